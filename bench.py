@@ -12,14 +12,16 @@ what a reference ``obs, r, done, _, _ = env.step(policy(obs))`` iteration produc
 an env step).  A pass is ONE launch over the batch (issued by a Python loop, a hipGraph replay or the library's C loop), or
 n_sub launches over n_sub contiguous sub-batches on n_sub HIP streams (jss_rollout_steps): step s of a sub-batch depends only
 on its own step s-1, so one sub-batch's drain overlaps another's fill; results are identical either way.  Which form: a short
-probe ranks them, every contender within 15 % of the best probe gets the full measurement, the best median is reported
-(best_form).
+probe ranks them, every contender within 15 % of the best probe gets the full measurement, the best median picks the form
+(best_form; its windows are reported as form_selection).
 
-Timing: W untimed warm-up steps, then windows of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides; per window the wall time is the MAX over ranks and the env steps the SUM
-over ranks (one RCCL all-reduce each, outside the timed region).  As many windows as it takes for the timed total to
-reach 0.55 s for the headline (0.1 s for the other configs; at least 5, at most 4 000 windows): the driver's K = 20 makes a
-window 0.3 ms, and a few of those are noise.  value = median window; n / min / p10 / max are printed too.  roofline.frac is
+Timing: W untimed warm-up steps, then the form selection above on windows of K steps; then the headline's state goes back
+to where the warm-up left it and EXACTLY K timed steps run in the chosen form (after at least 0.05 s of untimed passes over the same K steps),
+bracketed by barrier + torch.cuda.synchronize() on both sides.  value = env steps over the wall time of those K steps,
+ms_per_step = that time / K; the wall time is the MAX over ranks and the env steps the SUM over ranks (one RCCL all-reduce,
+outside the timed region).  --dump-outputs DIR writes what the last of the K steps returned.  The other configs time
+windows of exactly K steps, as many as it takes for the timed total to reach 0.1 s (at least 5, at most 4 000 windows),
+value = median window; n / min / p10 / max are printed too.  roofline.frac is
 value x algorithmic bytes / peak -- the wall-clock number anybody can recompute from the line; the HIP-event figure is kept
 as roofline.frac_gpu_time.
 
@@ -51,18 +53,16 @@ import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
+
+import numpy as np
 
 # Completion signals are polled instead of waited for through interrupts: a 20-step window is 0.25-0.4 ms of GPU
 # work, and the interrupt path adds tens of microseconds to every synchronize().  Process-wide HSA runtime setting,
 # must be in the environment before the runtime starts; reported in the JSON line (host.hsa_enable_interrupt).
 os.environ.setdefault("HSA_ENABLE_INTERRUPT", "0")
-# HIP deals streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) in creation order; two streams that share a queue
-# run strictly one after the other.  The pipelined forms use up to 5 streams (main + side streams of sub-batches or
-# shape buckets): 8 queues keep them apart whatever was created before (profiles/README.md: the bucketed env measured
-# 0.43-0.53 of the roofline inside the full bench with 4 queues, depending on which queues its streams drew).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -70,11 +70,12 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 HBM_MEASURED_PEAK_GBS = 6290.0  # measured copy bandwidth, same guide (SURVEY.md 8(d) asks for both)
-# windows per measurement: as many as it takes for the timed total to reach MIN_TIMED_SECONDS (the headline: half a second --
+# windows per measurement: as many as it takes for the timed total to reach MIN_TIMED_SECONDS (the headline's form selection: half a second --
 # at the driver's K = 20 a window is 0.3 ms, so that is ~1 600 windows; the other configs 0.1 s each, the step_only legs 0.05 s)
 MIN_WINDOWS, MAX_WINDOWS = 5, 4000
 MIN_TIMED_SECONDS_HEADLINE, MIN_TIMED_SECONDS, MIN_TIMED_SECONDS_LIGHT = 0.55, 0.1, 0.05
 CPU_BASELINE_SECONDS = 5.0
+WARM_SECONDS = 0.05             # untimed passes right before the headline's timed steps
 
 
 def csrc_hash():
@@ -291,6 +292,30 @@ def compact_line(out, detail_files=()):
     return text
 
 
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: data bytes in all, leaving room under 64 MB for the .npy headers
+
+
+def write_outputs(groups, out_dir, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: groups = {prefix: {name: array with the env index first}} -> out_dir/<prefix><name>.npy in float32.
+    When that would exceed max_bytes, every group keeps the same share of its envs: a sample fixed by `seed`, whose indices
+    go to <prefix>env_index.npy (float64).  Returns the file names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_env = {p: len(next(iter(arrays.values()))) for p, arrays in groups.items()}
+    total = sum(a.size * 4 for arrays in groups.values() for a in arrays.values())
+    keep = 1.0 if total <= max_bytes else max_bytes / (total + 8 * sum(n_env.values()))
+    written = []
+    for prefix, arrays in groups.items():
+        if keep < 1.0:
+            n = n_env[prefix]
+            idx = np.sort(np.random.default_rng(seed).choice(n, max(1, int(n * keep)), replace=False))
+            arrays = {"env_index": idx.astype(np.float64), **{k: np.asarray(a)[idx] for k, a in arrays.items()}}
+        for name, a in arrays.items():
+            a = np.asarray(a)
+            np.save(os.path.join(out_dir, prefix + name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+            written.append(prefix + name + ".npy")
+    return written
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -343,19 +368,23 @@ def parse_args():
                     help="also the side measurements (step_only, trajectory, external-action forms, facade, 4x batch, synthetic "
                          "15x15, the C-oracle / twin CPU baselines): minutes of extra run time, detail file only")
     ap.add_argument("--detail", default=None, help="where the unabridged JSON goes (default: bench_detail.json next to bench.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (real_obs, action_mask, reward, done) as "
+                         "DIR/<name>.npy in float32; the same arguments give the same inputs, so two builds compare output for output")
     return ap.parse_args()
 
 
 def respawn_under_torchrun(args):
-    """`python bench.py --gpus N` with N > 1 and no torchrun environment: become N ranks."""
-    import torch
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    """`python bench.py --gpus N` with N > 1 and no torchrun environment: run N ranks under torchrun as a child process."""
+    # the device count comes from a short-lived child: this process stays off the GPU while the N ranks hold it
+    probe = "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"
+    have = int(subprocess.check_output([sys.executable, "-c", probe], text=True).split()[-1])
     if have < args.gpus and not args.share_device:
         raise SystemExit(f"bench.py --gpus {args.gpus}: this node exposes {have} GPU(s); refusing to run "
                          f"{args.gpus} ranks on fewer devices (no oversubscription, no silent fallback to 1 GPU)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__), *sys.argv[1:]]
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def main():
@@ -553,16 +582,20 @@ def main():
         pick_mode.ranking = [(candidates[i], probe[i]) for i in order]      # (the headline re-measures a close runner-up)
         return candidates[order[0]]
 
+    def bind_window(env, policy, steps, mode):
+        """The pipelined forms' launch loop with every argument resolved here, so a timed region holds the call and nothing
+        else (None: the form has no such loop)."""
+        if mode.startswith("sub") and hasattr(env, "bind_rollout_steps") and not hasattr(env, "buckets") \
+                and os.environ.get("JSS_BENCH_FORK_JOIN", "0") != "1":
+            return env.bind_rollout_steps(policy, steps=steps, n_sub=int(mode[3:]), autoreset=True, caller_orders_streams=True)
+        return None
+
     def measure(env, policy, steps, mode, n_iter=1, windows=None, run=None, prep=None, min_seconds=MIN_TIMED_SECONDS):
         """Windows of `steps` steps each -- as many as it takes for the timed total to reach `min_seconds` (between
         MIN_WINDOWS and MAX_WINDOWS; every rank takes the same number).  Returns the median window and all windows,
         already reduced over ranks.  `run(n)` overrides what a window executes (extras)."""
         graph = capture(env, policy, steps) if mode == "graph" else None
-        bound = None
-        if run is None and graph is None and mode.startswith("sub") and hasattr(env, "bind_rollout_steps") and not hasattr(env, "buckets") \
-                and os.environ.get("JSS_BENCH_FORK_JOIN", "0") != "1":
-            # every argument of the window's launch loop resolved here: the timed region holds the call and nothing else
-            bound = env.bind_rollout_steps(policy, steps=steps, n_sub=int(mode[3:]), autoreset=True, caller_orders_streams=True)
+        bound = bind_window(env, policy, steps, mode) if run is None and graph is None else None
         window(env, policy, steps, n_iter, mode, graph, run, prep)           # untimed: side streams / graph exist before the first window
         first = min(window(env, policy, steps, n_iter, mode, graph, run, prep, bound=bound)[0] for _ in range(3))   # untimed: sizes the count
         if windows is None:
@@ -613,6 +646,39 @@ def main():
         results = [(m, *measure(env, policy, args.steps, m, min_seconds=min_seconds)) for m in contenders]
         rates = agree_max([r[1]["rate"] for r in results])
         return results[max(range(len(results)), key=lambda i: rates[i])]
+
+    def state_tensors(env):
+        """Everything a step reads or writes: the arena (state, counters, outputs) and the solution of every sub-batch."""
+        envs = [b for _, b in env._each()] if hasattr(env, "buckets") else [env]
+        return [t for e in envs for t in (e._arena, e.solution)]
+
+    def timed_steps(env, policy, steps, mode, start, gpu_ms_per_step_events):
+        """The headline's timed path: exactly `steps` steps in form `mode`, from the state `start` -- so what the last step
+        returns depends on the arguments alone, not on how many steps the form selection ran.  Untimed passes over the same
+        steps first, each from `start`, for at least WARM_SECONDS (graph upload, side streams, and a device that has been
+        busy rather than idle through the set-up: a short timed pass straight after it measured 13 % slow at K = 200)."""
+        graph = capture(env, policy, steps) if mode == "graph" else None
+        bound = bind_window(env, policy, steps, mode) if graph is None else None
+
+        def prep():
+            for t, s in zip(state_tensors(env), start):
+                t.copy_(s)
+            env.zero_counters()
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        first = window(env, policy, steps, 1, mode, graph, prep=prep, bound=bound)[0]
+        for _ in range(int(min(MAX_WINDOWS, agree_max([math.ceil(WARM_SECONDS / max(first, 1e-6))])[0]))):
+            window(env, policy, steps, 1, mode, graph, prep=prep, bound=bound)
+        dt, _ = window(env, policy, steps, 1, mode, graph, prep=prep, bound=bound)
+        if gc_was_on:
+            gc.enable()
+        del graph
+        tot = reduce_counters(env.counter_totals().cpu() if on_host else env.counter_totals(), dt, force_collectives=use_pg)
+        return {"steps": tot["steps"], "seconds": tot["seconds"], "rate": tot["steps"] / tot["seconds"],
+                "episodes": tot["episodes"], "makespan_sum": tot["makespan_sum"], "reward_num": tot["reward_num_sum"],
+                "rank_rate_min": tot["rank_rate_min"], "rank_rate_max": tot["rank_rate_max"],
+                "gpu_ms_per_step_events": gpu_ms_per_step_events}
 
     def window_stats(rows, steps):
         med = rows[len(rows) // 2]["rate"]
@@ -919,8 +985,17 @@ def main():
     for _ in range(args.warmup):
         env.rollout(args.policy, n_iter=1, autoreset=True)
     torch.cuda.synchronize()
-    mode, med, rows = best_form(env, args.policy, ["eager", "sub1", "sub2", "sub3"] if getattr(env, "_classes", None) is not None
-                                else ["eager", "graph", "sub1", "sub2", "sub3"], MIN_TIMED_SECONDS_HEADLINE)
+    start = [t.clone() for t in state_tensors(env)]
+    mode, sel, sel_rows = best_form(env, args.policy, ["eager", "sub1", "sub2", "sub3"] if getattr(env, "_classes", None) is not None
+                                    else ["eager", "graph", "sub1", "sub2", "sub3"], MIN_TIMED_SECONDS_HEADLINE)
+    med = timed_steps(env, args.policy, args.steps, mode, start, sel["gpu_ms_per_step_events"])
+    del start
+    dumped = None
+    if args.dump_outputs:
+        parts = [(f"bucket{k}_", b) for k, b in env._each()] if hasattr(env, "buckets") else [("", env)]
+        prefix = f"rank{rank}_" if world > 1 else ""
+        dumped = write_outputs({prefix + p: {k: getattr(e, k).cpu().numpy() for k in ("real_obs", "action_mask", "reward", "done")}
+                                for p, e in parts}, args.dump_outputs, max_bytes=DUMP_MAX_BYTES // world)
     # Host side of a window: what the C launch loop costs per launch (no synchronisation inside: the hardware queue holds a
     # whole window).  With N ranks on one host this is what must stay below the kernel time per launch -- MAX over ranks.
     host_issue_us = None
@@ -947,7 +1022,10 @@ def main():
         "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "int32",
         "data": ("ta01 (the reference's Taillard instance; no dataset involved)" if args.workload == "shared" and args.instance == "ta01"
                  else "synthetic" if args.workload.startswith("synthetic") else "reference instances (ta01-ta80)"),
-        "windows": window_stats(rows, args.steps),
+        "windows": window_stats([med], args.steps),
+        # the windows that chose the launch form (best_form), run before the timed steps from the same start state
+        "form_selection": {"value": sel["rate"], "windows": window_stats(sel_rows, args.steps)},
+        "dumped_outputs": dumped,
         "launch": ((f"one grid over all shape classes per step and part, {getattr(env, 'n_sub', 1)} part(s) per class (jss_multi_rollout, C launch loop)" if args.bucketed_launch == "grid" else
                     "one launch per shape bucket per step, every bucket on its own HIP stream (C launch loop)")
                    if hasattr(env, "buckets") else launch_label(mode)),

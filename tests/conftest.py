@@ -12,7 +12,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "refcheck: needs the live reference at /root/reference (build container only)")
 
 
 def _has_gpu():
@@ -25,12 +24,9 @@ def _has_gpu():
 
 def pytest_collection_modifyitems(config, items):
     has_gpu = _has_gpu()
-    has_ref = os.path.isfile("/root/reference/JSSEnv/envs/jss_env.py")
     for item in items:
         if "gpu" in item.keywords and not has_gpu:
             item.add_marker(pytest.mark.skip(reason="no GPU in this container"))
-        if "refcheck" in item.keywords and not has_ref:
-            item.add_marker(pytest.mark.skip(reason="live reference not present"))
 
 
 @pytest.fixture(scope="session")

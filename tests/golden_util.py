@@ -35,11 +35,12 @@ def check_env_against_row(env, g, i, where):
     assert len(env.next_time_step) == int(g["queue_len"][i]), f"{where}: queue length"
 
 
-def replay(env, g, obs_tol=None, check_state=True):
+def replay(env, g, obs_tol=None, check_state=True, after=None):
     """Replay a golden action trace through `env`; compare everything recorded.
 
     obs_tol None -> observation must be bit-equal float64 (oracle);
     otherwise |diff| <= obs_tol (float32 device path: 1e-6 per north_star).
+    after(env, i): further checks after row i.
     """
     obs_rows = {int(s): k for k, s in enumerate(g["obs_step"])}
     J = env.jobs
@@ -70,4 +71,6 @@ def replay(env, g, obs_tol=None, check_state=True):
                 assert (got == want).all(), f"{where}: obs not bit-equal, max diff {np.abs(got - want).max()}"
             else:
                 assert np.abs(got - want).max() <= obs_tol, f"{where}: obs max diff {np.abs(got - want).max()}"
+        if after is not None:
+            after(env, i)
     return env

@@ -106,3 +106,26 @@ def test_compact_line_of_a_multi_gpu_run_carries_the_rank_spread():
     line = bench.compact_line(out)
     d = json.loads(line)
     assert len(line) < bench.COMPACT_MAX_BYTES and d["ranks"] == {"value_min": 5.1e8, "value_max": 5.4e8, "numa_pinned": True}
+
+
+def test_dump_outputs_stay_under_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 files; over the byte budget every array keeps the same seeded sample of envs, the same from
+    run to run, and the indices are written next to them."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    B = 1000
+    arrays = {"real_obs": rng.random((B, 20, 7), dtype=np.float32), "action_mask": rng.integers(0, 2, (B, 21), dtype=np.uint8),
+              "reward": rng.random(B, dtype=np.float32), "done": rng.integers(0, 2, B, dtype=np.uint8)}
+    small = bench.write_outputs({"": arrays}, str(tmp_path / "all"))
+    assert sorted(small) == ["action_mask.npy", "done.npy", "real_obs.npy", "reward.npy"]
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    budget = 200_000
+    for d in ("a", "b"):
+        files = bench.write_outputs({"": arrays}, str(tmp_path / d), max_bytes=budget)
+        assert sum(np.load(tmp_path / d / f).nbytes for f in files) <= budget
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < B and np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    got = np.load(tmp_path / "a" / "real_obs.npy")
+    assert np.array_equal(got, arrays["real_obs"][idx.astype(int)]) and np.array_equal(got, np.load(tmp_path / "b" / "real_obs.npy"))

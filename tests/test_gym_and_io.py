@@ -187,42 +187,27 @@ def test_schedule_gif_is_written_without_imageio(tmp_path):
     assert frame.shape == (270, 480, 3) and frame.dtype == np.uint8 and (frame != 255).any()
 
 
-@pytest.mark.refcheck
 def test_render_rows_equal_the_reference():
-    """Build container only: the rows handed to create_gantt equal the reference's render() dataframe for the same
-    schedule (jss_env.py:666-677)."""
-    tools = os.path.join(ROOT, "tools")
-    sys.path.insert(0, tools)
-    import refload
-    if not refload.reference_available():
-        pytest.skip("reference tree absent")
+    """The rows handed to create_gantt equal the reference's render() dataframe for the same schedule
+    (jss_env.py:666-677): 60 random steps on ta01, the reference's rows and trace count recorded in golden/walks.npz."""
     pytest.importorskip("plotly")
+    import datetime
+    import golden_util as G
     from jssenv_amd import make
     from jssenv_amd.render import gantt_rows
-    Ref, _ = refload.load_reference()
-    ref = Ref({"instance_path": refload.reference_instance_path("ta01")})
+    g = G.load("walks")
     env = make("jss-v1", env_config={"instance_path": "ta01"}, device="cpu")
-    ref.reset()
     env.reset()
-    rng = np.random.default_rng(1)
-    for _ in range(60):
-        a = int(rng.choice(np.flatnonzero(ref.legal_actions)))
-        ref.step(a)
-        env.step(a)
-    fig = ref.render()
-    mine = gantt_rows(env.solution, env.instance, ref.start_timestamp)
-    import datetime
-    want = []
-    for job in range(ref.jobs):
-        for k in range(ref.machines):
-            if ref.solution[job][k] == -1:
-                break
-            s0 = ref.start_timestamp + ref.solution[job][k]
-            want.append({"Task": f"Job {job}", "Start": datetime.datetime.fromtimestamp(s0),
-                         "Finish": datetime.datetime.fromtimestamp(s0 + ref.instance_matrix[job][k][1]),
-                         "Resource": f"Machine {ref.instance_matrix[job][k][0]}"})
-    assert mine == want and fig is not None
-    assert len(env.render().data) == len(fig.data)
+    for a in g["render_ta01_action"]:
+        assert env.legal_actions[a]
+        env.step(int(a))
+    t0 = env.start_timestamp
+    mine = gantt_rows(env.solution, env.instance, t0)
+    want = [{"Task": f"Job {job}", "Start": datetime.datetime.fromtimestamp(t0 + int(s)),
+             "Finish": datetime.datetime.fromtimestamp(t0 + int(f)), "Resource": f"Machine {m}"}
+            for job, s, f, m in g["render_ta01_rows"]]
+    assert mine == want
+    assert len(env.render().data) == int(g["render_ta01_traces"])
 
 
 def _facade_attribute_walk(ref, env, rng, episodes=2, with_advance=False):
@@ -276,17 +261,27 @@ def test_facade_next_jobs_colors_start_timestamp(name):
     assert env.next_jobs == [] and env.next_time_step == []
 
 
-@pytest.mark.refcheck
 def test_facade_next_jobs_equal_the_reference():
-    """Build container only: the same walk against the live reference's own lists."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import refload
-    if not refload.reference_available():
-        pytest.skip("reference tree absent")
+    """The same walk against the reference's own lists: its next_time_step / next_jobs after every call of two random
+    episodes with forced NOPEs (seed 9), and its number of colors, recorded in golden/walks.npz."""
+    import golden_util as G
     from jssenv_amd import make
-    Ref, _ = refload.load_reference()
+    g = G.load("walks")
     for name in ("ta01", "ta41"):
-        ref = Ref({"instance_path": refload.reference_instance_path(name)})
+        w = {k: g[f"walk_{name}_{k}"] for k in ("action", "next_time_step", "next_time_step_off", "next_jobs", "next_jobs_off")}
         env = make("jss-v1", env_config={"instance_path": name}, device="cpu")
-        _facade_attribute_walk(ref, env, np.random.default_rng(9), episodes=2)
-        assert hasattr(ref, "colors") and hasattr(ref, "start_timestamp") and len(env.colors) == len(ref.colors)
+        env.reset()
+        n = 0
+        for a in w["action"]:
+            if a == -2:                                        # the next episode
+                env.reset()
+                assert env.next_jobs == [] and env.next_time_step == []
+                continue
+            env.step(int(a))
+            lo, hi = w["next_time_step_off"][n:n + 2]
+            assert env.next_time_step == w["next_time_step"][lo:hi].tolist(), n
+            lo, hi = w["next_jobs_off"][n:n + 2]
+            assert env.next_jobs == w["next_jobs"][lo:hi].tolist(), (n, env.next_jobs)
+            n += 1
+        assert n == len(w["next_time_step_off"]) - 1
+        assert hasattr(env, "start_timestamp") and len(env.colors) == int(g[f"walk_{name}_colors"])

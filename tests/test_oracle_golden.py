@@ -128,24 +128,16 @@ def test_total_semantics_outside_the_reference_contract():
     assert env.err & 4
 
 
-@pytest.mark.refcheck
-def test_oracle_vs_live_reference_lockstep():
-    """Build container only: drive reference and oracle side by side (float64-exact)."""
-    import sys, os
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import lockstep as L
-    rng = np.random.default_rng(5)
+def test_oracle_vs_reference_lockstep():
+    """G5: the oracle in lock step with the reference's random masked traces (~5 % NOPEs forced against the mask):
+    every integer, the solution, illegal_actions, the event queue and the float64 observation after every call."""
     for name in ("ta03", "ta33", "dmu18"):
-        ref, orc = L.make_pair(name)
-        done, n = False, 0
-        while not done:
-            m = np.asarray(ref.legal_actions)
-            if rng.random() < 0.05 and len(ref.next_time_step) > 0 and m[:-1].any():
-                a = ref.jobs
-            else:
-                a = int(rng.choice(np.flatnonzero(m)))
-            try:
-                _, _, done = L.step_both(ref, orc, a, f"{name} step {n}")
-            except IndexError:
-                break
-            n += 1
+        g = G.load(f"lockstep_{name}")
+        queue, off = g["next_time_step"], g["next_time_step_off"]
+
+        def lockstep(env, i):
+            assert (np.asarray(env.solution) == g["solution"][i]).all(), f"{name} row {i}: solution"
+            assert (np.asarray(env.illegal_actions).astype(bool) == g["illegal_actions"][i]).all(), f"{name} row {i}: illegal_actions"
+            assert list(env.next_time_step) == queue[off[i]:off[i + 1]].tolist(), f"{name} row {i}: queue"
+        env = OracleEnv(I.builtin_instance(name))
+        G.replay(env, g, after=lockstep)

@@ -10,7 +10,6 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_INTERRUPT", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from jssenv_amd import BatchedJssEnv, builtin_instance  # noqa: E402

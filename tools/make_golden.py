@@ -19,8 +19,16 @@ the gymnasium stand-in of tools/refload.py; nothing of it is copied.
                              action trace per (rule, instance).
   G4  rules_seeded.npz       FIFO/SPT with the reference's 10 % NOPE exploration
                              under np.random.seed(s): action trace + makespan.
+  G5  lockstep_<inst>.npz    seeded random masked traces (~5 % NOPEs forced) on
+                             ta03 / ta33 / dmu18 in G2's layout, the float64
+                             observation, the event queue, the solution and
+                             illegal_actions after every call.
+      walks.npz              the reference's next_time_step / next_jobs lists
+                             after every call of random episodes with forced
+                             NOPEs (ta01, ta41), and the Gantt rows and trace
+                             count of render() after 60 random steps on ta01.
 
-Run:  python tools/make_golden.py
+Run:  python tools/make_golden.py [G1 G2 G3 G4 G5]     (no argument: all of them)
 """
 import os
 import sys
@@ -201,11 +209,93 @@ def g4_rules_seeded():
     np.savez_compressed(os.path.join(OUT, "rules_seeded.npz"), **out)
 
 
+def _ragged(lists):
+    """A list of int lists -> (flat int32, offsets int32 with len(lists) + 1 entries)."""
+    off = np.cumsum([0] + [len(x) for x in lists]).astype(np.int32)
+    return np.asarray([int(v) for x in lists for v in x], dtype=np.int32), off
+
+
+def g5_walks():
+    for inst in ("ta03", "ta33", "dmu18"):
+        rng = np.random.default_rng(5)
+        env = new_ref(inst)
+        rec = Recorder(env, obs_every=1)
+        rec.snap(-2, 0.0, False)                       # -2 = reset()
+        queues, extra = [list(env.next_time_step)], {"solution": [], "illegal_actions": []}
+
+        def snap_extra():
+            extra["solution"].append(np.asarray(env.solution, dtype=np.int16).copy())
+            extra["illegal_actions"].append(np.asarray(env.illegal_actions, dtype=bool).copy())
+        snap_extra()
+        done = False
+        while not done:
+            m = np.asarray(env.legal_actions)
+            if rng.random() < 0.05 and len(env.next_time_step) > 0 and m[:-1].any():
+                a = env.jobs
+            else:
+                a = int(rng.choice(np.flatnonzero(m)))
+            try:                                       # (a forced NOPE can dead-lock the reference: see G2)
+                _, rew, done, _, _ = env.step(a)
+            except IndexError:
+                break
+            rec.snap(a, rew, done)
+            queues.append(list(env.next_time_step))
+            snap_extra()
+        arrs = rec.arrays()
+        arrs.update({k: np.stack(v) for k, v in extra.items()})
+        arrs["next_time_step"], arrs["next_time_step_off"] = _ragged(queues)
+        np.savez_compressed(os.path.join(OUT, f"lockstep_{inst}.npz"), **arrs)
+        print(f"G5 lockstep {inst}: {rec.n} calls")
+
+    out = {}
+    for inst in ("ta01", "ta41"):                      # the facade walk of tests/test_gym_and_io.py, seed 9, two episodes
+        rng = np.random.default_rng(9)
+        env = new_ref(inst)
+        actions, nts, nj = [], [], []
+        for _ in range(2):
+            env.reset()
+            done, n = False, 0
+            while not done:
+                a = int(rng.choice(np.flatnonzero(env.legal_actions)))
+                if n % 11 == 5 and len(env.next_time_step) > 0 and env.legal_actions[:-1].sum() > 0:
+                    a = env.jobs
+                _, _, done, _, _ = env.step(a)
+                n += 1
+                actions.append(a)
+                nts.append(list(env.next_time_step))
+                nj.append(list(env.next_jobs))
+            actions.append(-2)                         # -2 = the next episode's reset()
+        out[f"walk_{inst}_action"] = np.asarray(actions, dtype=np.int16)
+        out[f"walk_{inst}_next_time_step"], out[f"walk_{inst}_next_time_step_off"] = _ragged(nts)
+        out[f"walk_{inst}_next_jobs"], out[f"walk_{inst}_next_jobs_off"] = _ragged(nj)
+        out[f"walk_{inst}_colors"] = np.int32(len(env.colors))
+        print(f"G5 walk {inst}: {len(nts)} calls")
+
+    rng = np.random.default_rng(1)                     # render(): 60 random steps on ta01
+    env = new_ref("ta01")
+    actions = []
+    for _ in range(60):
+        a = int(rng.choice(np.flatnonzero(env.legal_actions)))
+        env.step(a)
+        actions.append(a)
+    rows = []                                          # (job, start, finish, machine), times relative to start_timestamp
+    for job in range(env.jobs):
+        for k in range(env.machines):
+            if env.solution[job][k] == -1:
+                break
+            s0 = int(env.solution[job][k])
+            rows.append((job, s0, s0 + int(env.instance_matrix[job][k][1]), int(env.instance_matrix[job][k][0])))
+    out["render_ta01_action"] = np.asarray(actions, dtype=np.int16)
+    out["render_ta01_rows"] = np.asarray(rows, dtype=np.int32)
+    out["render_ta01_traces"] = np.int32(len(env.render().data))
+    np.savez_compressed(os.path.join(OUT, "walks.npz"), **out)
+    print(f"G5 render ta01: {len(rows)} rows")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    g1_published()
-    g2_random()
-    g3_rules()
-    g4_rules_seeded()
+    sections = {"G1": g1_published, "G2": g2_random, "G3": g3_rules, "G4": g4_rules_seeded, "G5": g5_walks}
+    for name in sys.argv[1:] or sections:
+        sections[name]()
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print(f"golden fixtures: {total / 1024:.0f} KiB in {OUT}")

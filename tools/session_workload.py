@@ -15,7 +15,6 @@ import sys
 import time
 
 os.environ.setdefault("HSA_ENABLE_INTERRUPT", "0")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
