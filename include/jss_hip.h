@@ -41,6 +41,9 @@
  *                   an env that reported done on the previous call is reset instead of stepped, in the same launch
  *   jss_policy_step_steps <- the un-fused loop `a = policy(obs); obs, r, done, _, _ = env.step(a)` (README.md:53-64), K
  *                   times, policy and step as launches of their own, pipelined over sub-batches
+ *   jss_step_logits <- the step of an on-policy learner: `a ~ softmax(logits masked by action_mask)` (the caller's policy
+ *                   network's output), log pi(a) and the entropy, then JssEnv.step(a) -- the masked categorical draw fused
+ *                   into the step launch
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer in JssDesc/JssState/JssOut is a
@@ -81,7 +84,7 @@
 extern "C" {
 #endif
 
-#define JSS_ABI_VERSION 10
+#define JSS_ABI_VERSION 11
 
 #define JSS_MAX_JOBS 128
 #define JSS_MAX_MACHINES 64
@@ -193,6 +196,7 @@ extern "C" {
 #define JSS_ERR_ILLEGAL_ACTION 1 /* job action outside the mask: ignored (reference: silent corruption) */
 #define JSS_ERR_NOPE_IDLE 2      /* NOPE/advance with no busy machine (reference: IndexError, jss_env.py:517) */
 #define JSS_ERR_BAD_ACTION 4     /* action < -2 or > J: ignored (reference: IndexError) */
+#define JSS_ERR_BAD_LOGITS 8     /* jss_step_logits: a legal action's logit was NaN or +inf (read as -inf) */
 
 #define JSS_ACTION_SKIP (-1) /* batched step: this env is not stepped; its state, reward, done and makespan
                                 are left as they were (observation and mask are rewritten unchanged) */
@@ -475,6 +479,50 @@ int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState
 int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                       int kind, uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub,
                       void *const *streams);
+
+/* ---- step from the caller's logits ------------------------------------------------------------------------------
+ * jss_step_logits = jss_policy with the caller's masked categorical distribution followed by jss_step (jss_step_autoreset
+ * with flags & JSS_ROLLOUT_AUTORESET), in ONE launch: state, `out` and the counters end bit-identical to jss_step(desc,
+ * state, actions = lg->action, out) (resp. jss_step_autoreset).  Per env i, with the header's episode and step BEFORE
+ * the call (the key of the random policy) and env_id as for jss_policy:
+ *   - autoreset and out->done[i] set: the env is reset; action JSS_ACTION_RESET, logp 0, entropy 0.
+ *   - no legal action (and no reset): the env is left as jss_step leaves it for JSS_ACTION_SKIP; action JSS_ACTION_SKIP,
+ *     logp 0, entropy 0.
+ *   - otherwise the entries that take part are the legal ones only: job j (< J(env)) whose mask bit is set, and NOPE
+ *     (index J(env)) when NOPE is legal.  Entries behind J(env) (the padding of a ragged batch) are never read as actions.
+ *     l_a = logit of action a; a NaN or +inf l_a sets JSS_ERR_BAD_LOGITS in the env's status byte and is read as -inf.
+ *     T = temperature.  T > 0 samples by Gumbel-max, in float32:
+ *         r_a = fmix32(rng_u32(seed ^ JSS_LOGITS_SEED_XOR, env_id, episode, step) + a * 0x9E3779B9u)
+ *         u_a = ((r_a >> 8) + 0.5f) * 2^-24          (in (0, 1), exact)
+ *         g_a = -logf(-logf(u_a))                     (the precise logf)
+ *         action = argmax over the legal a of (l_a / T + g_a), the lowest index on ties
+ *     (fmix32 / rng_u32: the counter RNG of the random policy, oracle/jss_oracle.c orc_rng_u32); T == 0 is greedy: the
+ *     argmax of l_a, the lowest index on ties.  Ties are float comparisons: -0 ties with +0.  Every legal entry -inf: the
+ *     lowest legal action (a job before NOPE).
+ *   - logp / entropy of the masked distribution softmax(l / T) (T == 0: reported for T = 1), float32, precise expf / logf:
+ *         x_a = l_a / T,  m = max x_a,  s = sum exp(x_a - m),  logp = (x_action - m) - log s,
+ *         entropy = log s + m - sum exp(x_a - m) * x_a / s          (the sums over the legal a with x_a > -inf)
+ *     The order of the summation is the library's own (the kernels reduce by lane tree, the host twin in index order):
+ *     the two libraries agree on logp / entropy to float32 rounding, not bit for bit.
+ *     Every legal entry -inf: logp = -inf, entropy 0.
+ * An env that was never reset is left alone (its action / logp / entropy entries are not written), as by jss_policy.
+ * Errors: JSS_E_NULL for a NULL lg, lg->logits or lg->action; JSS_E_SHAPE for a row other than 0 outside [jmax + 1, 2^24];
+ * JSS_E_KIND for an unknown dtype or a temperature < 0 or NaN. */
+#define JSS_LOGITS_F32 0
+#define JSS_LOGITS_BF16 1   /* the upper 16 bits of a float32, widened exactly (<< 16) */
+#define JSS_LOGITS_SEED_XOR 0x2545F4914F6CDD1DULL   /* K_LOGITS: keys the Gumbel noise apart from the random policy's draws */
+typedef struct JssLogits {
+    const void *logits;  /* [B][row], laid out like action_mask: job j at j, NOPE at J(env), ignored behind it        */
+    int64_t row;         /* elements between env i and env i + 1; 0 = jmax + 1; otherwise jmax + 1 <= row <= 2^24
+                            (JSS_E_SHAPE outside: the kernels address a row by 32-bit lane offsets)              */
+    int32_t dtype;       /* JSS_LOGITS_F32 / JSS_LOGITS_BF16                                                        */
+    float temperature;   /* > 0: sample from softmax(logits / T); 0: greedy (argmax, lowest index on ties)           */
+    int32_t *action;     /* [B] out: the action taken (job, J = NOPE), JSS_ACTION_RESET or JSS_ACTION_SKIP (never NULL) */
+    float *logp;         /* [B] out, may be NULL: log-probability of `action` under the masked distribution          */
+    float *entropy;      /* [B] out, may be NULL: entropy of the masked distribution                                 */
+} JssLogits;
+int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
+                    const JssOut *out, void *stream);
 
 #ifdef JSS_PROFILING
 /* Instrumented builds only (tools/build_instrumented.py compiles with -DJSS_PROFILING; the shipped library does

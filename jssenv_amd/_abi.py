@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 STATE_LAYOUT = 7     # version of the state tensors' layout (checkpoints): unchanged since ABI v7
 MAX_JOBS, MAX_MACHINES = 128, 64
 F_TODO, F_CUR, F_LEFT, F_PERF, F_IDLE, F_IDLE_LAST, F_F4, F_NEXT, NF = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -28,10 +28,13 @@ STATUS_NOOP = 256
 F4_ONE = -1
 I_JOBS, I_MACHINES, I_MAX_TIME_OP, I_MAX_TIME_JOBS, I_SUM_OP = 0, 1, 2, 3, 4
 I_RCP_MAX_TIME_OP, I_RCP_MAX_TIME_JOBS, I_RCP_SUM_OP, I_RCP_MACHINES, NI = 5, 6, 7, 8, 12
-ERR_ILLEGAL_ACTION, ERR_NOPE_IDLE, ERR_BAD_ACTION = 1, 2, 4
+ERR_ILLEGAL_ACTION, ERR_NOPE_IDLE, ERR_BAD_ACTION, ERR_BAD_LOGITS = 1, 2, 4, 8
 ACTION_SKIP, ACTION_RESET, ACTION_CLOSE = -1, -2, -3
 POLICY = {"random": 0, "FIFO": 1, "SPT": 2, "MWR": 3, "LWR": 4, "MOR": 5, "LOR": 6, "CR": 7}
 ROLLOUT_AUTORESET, ROLLOUT_FORK_JOIN = 1, 2
+# jss_step_logits (JssLogits.dtype; K_LOGITS keys its Gumbel noise: rng_u32(seed ^ LOGITS_SEED_XOR, ...))
+LOGITS_F32, LOGITS_BF16 = 0, 1
+LOGITS_SEED_XOR = 0x2545F4914F6CDD1D
 
 
 def cr_kind(due_date_factor: float = 1.5):
@@ -62,7 +65,7 @@ MAX_SUB_BATCHES = 16
 SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "jss_step", "jss_advance", "jss_policy",
            "jss_rollout", "jss_rollout_steps", "jss_rollout_steps_multi", "jss_trajectory", "jss_sync_check",
            "jss_step_autoreset", "jss_policy_step_steps", "jss_steps", "jss_session_open", "jss_session_post", "jss_session_wait", "jss_session_step", "jss_session_close",
-           "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout")
+           "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits")
 
 _p = C.c_void_p
 
@@ -91,6 +94,11 @@ class JssTraj(C.Structure):
 class JssSession(C.Structure):
     _fields_ = [("mail", _p), ("progress", _p), ("status", _p), ("depth", C.c_int32), ("timeout_ms", C.c_int32),
                 ("slots", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JssLogits(C.Structure):
+    _fields_ = [("logits", _p), ("row", C.c_int64), ("dtype", C.c_int32), ("temperature", C.c_float),
+                ("action", _p), ("logp", _p), ("entropy", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -143,6 +151,8 @@ def bind(lib):
     lib.jss_session_wait.restype, lib.jss_session_wait.argtypes = C.c_int, [D, SS, C.c_int32, _p]
     lib.jss_session_close.restype, lib.jss_session_close.argtypes = C.c_int, [D, SS, C.c_int32, _p]
     lib.jss_session_step.restype, lib.jss_session_step.argtypes = C.c_int, [D, SS, _p, C.c_int32, _p]
+    lib.jss_step_logits.restype = C.c_int
+    lib.jss_step_logits.argtypes = [D, S, C.POINTER(JssLogits), C.c_uint64, C.c_int32, O, _p]
     if lib.jss_abi_version() != ABI_VERSION:
         raise RuntimeError(f"library ABI {lib.jss_abi_version()} != expected {ABI_VERSION}")
     return lib

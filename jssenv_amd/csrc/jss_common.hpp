@@ -38,6 +38,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>   // logf / expf (jss_step_logits): the precise ones, on the device pass and on the emulator's host pass
+
 #include "jss_hip.h"
 
 namespace jss {
@@ -54,7 +56,10 @@ constexpr int kDurMask = 0xffff;
 // kSteps = n_iter x kStep per launch with the actions given up front ([K][B]), optionally recording every step (JssTraj)
 // kSession = kStep's semantics inside the resident step-session kernel (outputs write-through, counters tallied in
 //            registers until the session closes); only the session kernels are instantiated with it
-enum Mode { kReset = 0, kStep = 1, kAdvance = 2, kPolicy = 3, kRollout = 4, kRollout1 = 5, kTraj = 6, kSteps = 7, kSession = 8 };
+// kLogits = kStep with the action drawn in the kernel from the caller's logits (jss_step_logits: masked Gumbel-max,
+//           log-probability and entropy)
+enum Mode { kReset = 0, kStep = 1, kAdvance = 2, kPolicy = 3, kRollout = 4, kRollout1 = 5, kTraj = 6, kSteps = 7, kSession = 8,
+            kLogits = 9 };
 // where the op table lives: LDS (one instance shared by the batch) or global memory; kTabLdsC = LDS + compact 16-byte
 // job records (the three cached ops are re-read from the LDS table, the machine clocks rebuilt from the records)
 // kTabGlobalM = global memory + 24-byte medium records (packed kernels only: jobs, machines <= 32; the three cached ops in 21
@@ -96,6 +101,7 @@ struct Params {
     int32_t slots;                    // env sets per wavefront (1, 2, 4, 8)
     int32_t park_off_ints;            // LDS offset (ints) of the parked env sets: [wave][slot][kParkInt4][64 lanes] int4
     int32_t norm_slot_ints;           // packed kernel, kTabGlobal: ints between two slots' normaliser tables
+    JssLogits lg;                     // kLogits (row resolved: >= jmax + 1)
 #ifdef JSS_PROFILING
     unsigned long long *stamps;       // instrumented builds: [B][16] shader-clock stamps of the one-wavefront-per-env kernels (JSS_STAMP)
 #endif
@@ -406,5 +412,67 @@ __device__ __forceinline__ CrKeyF cr_argmin_f64(CrKeyF k) {   // butterfly insid
 constexpr double kCrInf = __builtin_huge_val();
 
 constexpr uint64_t kExploreSeedXor = 0x5851F42D4C957F2DULL;
+constexpr uint64_t kLogitsSeedXor = JSS_LOGITS_SEED_XOR;   // K_LOGITS (include/jss_hip.h, jss_step_logits)
+
+// ---- jss_step_logits: masked Gumbel-max over the caller's logits (formulas: include/jss_hip.h) ----------------------
+// A float crosses lanes as its bit pattern (DPP / swizzle / readlane move ints).  Order-preserving int key of a float that
+// is not NaN: signed compare of ord_key(a) vs ord_key(b) == float compare of a vs b, -0 and +0 included (they compare equal:
+// x + 0 turns -0 into +0 and leaves every other value as it is, so both get +0's key and the lowest index wins their tie);
+// kOrdNone is below every such key (-inf included), the key of an entry that does not take part.
+__device__ __forceinline__ int ord_key(float x) {
+    const int b = as_int(x + 0.f);
+    return b >= 0 ? b : b ^ 0x7FFFFFFF;
+}
+__device__ __forceinline__ float ord_float(int k) { return as_float(k >= 0 ? k : k ^ 0x7FFFFFFF); }
+constexpr int kOrdNone = (int)0x80000000;
+// logit bits as loaded (float32, or bfloat16 in the low half) -> float32
+__device__ __forceinline__ float logit_of(int raw, int dtype) { return as_float(dtype == JSS_LOGITS_BF16 ? raw << 16 : raw); }
+// float sum over the 16 lanes of a DPP row, result in every lane of the row
+__device__ __forceinline__ float row_fsum(float v) {
+    v += as_float(JSS_DPP(as_int(v), 0xB1));
+    v += as_float(JSS_DPP(as_int(v), 0x4E));
+    v += as_float(JSS_DPP(as_int(v), 0x141));
+    v += as_float(JSS_DPP(as_int(v), 0x140));
+    return v;
+}
+// One legal entry: x = l / T (l when T == 0, greedy), its Gumbel-max score (r = rng_u32(seed ^ K_LOGITS, ...) of the env),
+// `bad` = a NaN / +inf logit (read as -inf).  Keys: score, x (for the max), both kOrdNone when the entry does not take part.
+struct LgEntry {
+    int skey, xkey;
+    float x;
+    bool bad;
+};
+__device__ __forceinline__ LgEntry lg_entry(float l, bool part, int a, uint32_t r, float temperature) {
+    LgEntry en;
+    en.bad = part && (__builtin_isnan(l) || l == __builtin_huge_valf());
+    if (en.bad) l = -__builtin_huge_valf();
+    en.x = temperature > 0.f ? l / temperature : l;
+    float score = en.x;
+    if (temperature > 0.f) {
+        const uint32_t ra = fmix32(r + (uint32_t)a * 0x9E3779B9u);
+        const float u = ((float)(ra >> 8) + 0.5f) * 5.9604644775390625e-8f;   // 2^-24
+        score += -logf(-logf(u));
+    }
+    en.skey = part ? ord_key(score) : kOrdNone;
+    en.xkey = part ? ord_key(en.x) : kOrdNone;
+    return en;
+}
+// exp(x - m) and exp(x - m) * x of one entry (0 for an entry that does not take part or is -inf)
+__device__ __forceinline__ void lg_terms(const LgEntry &en, float m, float &w, float &wx) {
+    const bool live = en.xkey != kOrdNone && en.x > -__builtin_huge_valf();
+    w = live ? expf(en.x - m) : 0.f;
+    wx = live ? w * en.x : 0.f;
+}
+// logp of the action with x = xa, and the entropy, from m, s = sum w and sx = sum w x
+__device__ __forceinline__ void lg_finish(float m, float s, float sx, float xa, float &logp, float &entropy) {
+    if (!(m > -__builtin_huge_valf())) {                 // every legal entry -inf
+        logp = -__builtin_huge_valf();
+        entropy = 0.f;
+        return;
+    }
+    const float ls = logf(s);
+    logp = (xa - m) - ls;
+    entropy = ls + m - sx / s;
+}
 
 }  // namespace jss

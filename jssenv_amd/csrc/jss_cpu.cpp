@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <unordered_map>
 
@@ -23,6 +24,7 @@ namespace {
 constexpr int kBig = 0x3fffffff;
 constexpr int kDurMask = 0xffff;
 constexpr uint64_t kExploreSeedXor = 0x5851F42D4C957F2DULL;
+constexpr uint64_t kLogitsSeedXor = JSS_LOGITS_SEED_XOR;
 
 struct Call {   // one ABI call
     JssDesc d;
@@ -38,6 +40,7 @@ struct Call {   // one ABI call
     int kind = 0;
     int n_iter = 0;
     int flags = 0;
+    JssLogits lg = JssLogits();   // jss_step_logits (row resolved)
 };
 
 // One env: pointers into the batch tensors + its instance.
@@ -486,12 +489,66 @@ int select_action(const Env &e, const Call &c, uint64_t env_id) {
     return best;
 }
 
-// ---- outputs ------------------------------------------------------------------------------------------------
 float as_float(int32_t bits) {
     float f;
     std::memcpy(&f, &bits, 4);
     return f;
 }
+
+// jss_step_logits: Gumbel-max over the legal entries of env b's logits row, in float32, the kernels' formula and order of
+// operations (include/jss_hip.h).  Returns JSS_ACTION_SKIP when nothing is legal.
+int select_logits(const Env &e, const Call &c, int b, uint64_t env_id, float &logp, float &entropy, bool &bad) {
+    logp = entropy = 0.f;
+    bad = false;
+    if (n_legal(e) + e.noop() == 0) return JSS_ACTION_SKIP;
+    const uint32_t r = rng_u32(c.seed ^ kLogitsSeedXor, env_id, (uint32_t)e.hdr[JSS_H_EPISODE], (uint32_t)e.hdr[JSS_H_STEP]);
+    const float T = c.lg.temperature;
+    const float inf = std::numeric_limits<float>::infinity();
+    float x[JSS_MAX_JOBS + 1];
+    bool part[JSS_MAX_JOBS + 1];
+    int best = -1;
+    float best_score = 0.f, m = -inf;
+    for (int a = 0; a <= e.J; ++a) {
+        part[a] = a < e.J ? e.legal(a) : e.noop() != 0;
+        if (!part[a]) continue;
+        const size_t at = (size_t)b * c.lg.row + a;
+        float l = c.lg.dtype == JSS_LOGITS_BF16 ? as_float((int32_t)((uint32_t)static_cast<const uint16_t *>(c.lg.logits)[at] << 16))
+                                                : static_cast<const float *>(c.lg.logits)[at];
+        if (std::isnan(l) || l == inf) {                                  // read as -inf, flagged
+            bad = true;
+            l = -inf;
+        }
+        x[a] = T > 0.f ? l / T : l;
+        float score = x[a];
+        if (T > 0.f) {
+            const uint32_t ra = fmix32(r + (uint32_t)a * 0x9E3779B9u);
+            const float u = ((float)(ra >> 8) + 0.5f) * 5.9604644775390625e-8f;   // 2^-24
+            score += -logf(-logf(u));
+        }
+        if (best < 0 || score > best_score) {                             // strict: the lowest index wins ties
+            best = a;
+            best_score = score;
+        }
+        if (x[a] > m) m = x[a];
+    }
+    if (!(m > -inf)) {                                                    // every legal entry -inf
+        logp = -inf;
+        return best;
+    }
+    float s = 0.f, sx = 0.f;
+    for (int a = 0; a <= e.J; ++a) {
+        if (!part[a] || !(x[a] > -inf)) continue;
+        const float w = expf(x[a] - m);
+        s += w;
+        sx += w * x[a];
+    }
+    const float ls = logf(s);
+    logp = (x[best] - m) - ls;
+    entropy = ls + m - sx / s;
+    return best;
+}
+
+// ---- outputs ------------------------------------------------------------------------------------------------
 // the kernels' division: quotient estimate with the record's reciprocal, one residual correction (bit-identical)
 float div_by(float a, float b, float rb) {
     const float q = a * rb;
@@ -544,7 +601,7 @@ void add_counters(const Call &c, int b, int steps, int episodes, long long makes
 
 uint64_t env_id_of(const Call &c, int b) { return (uint64_t)(c.d.env_ids ? c.d.env_ids[b] : c.d.env_id_base + b); }
 
-enum Mode { kReset, kStep, kAdvance, kPolicy, kRollout, kTraj, kSteps };
+enum Mode { kReset, kStep, kAdvance, kPolicy, kRollout, kTraj, kSteps, kLogits };
 
 void restart(const Env &e, const Call &c, int b) {                       // reset() + the bookkeeping around it
     const int episode = e.hdr[JSS_H_EPISODE];
@@ -592,6 +649,19 @@ void run_env(const Call &c, int mode, int b) {
         int rn;
         // jss_step_autoreset: an env that reported done on the previous call is reset instead of stepped
         const int a = ((c.flags & JSS_ROLLOUT_AUTORESET) && c.o.done[b]) ? JSS_ACTION_RESET : c.actions[b];
+        step_call(e, c, b, a, called, rn);
+        break;
+    }
+    case kLogits: {                                                       // jss_step_logits: the draw, then kStep with it
+        bool called, bad = false;
+        int rn;
+        float logp = 0.f, entropy = 0.f;
+        int a = ((c.flags & JSS_ROLLOUT_AUTORESET) && c.o.done[b]) ? JSS_ACTION_RESET : JSS_ACTION_SKIP;
+        if (a != JSS_ACTION_RESET) a = select_logits(e, c, b, env_id_of(c, b), logp, entropy, bad);
+        if (bad) e.flag(JSS_ERR_BAD_LOGITS);
+        c.lg.action[b] = a;
+        if (c.lg.logp) c.lg.logp[b] = logp;
+        if (c.lg.entropy) c.lg.entropy[b] = entropy;
         step_call(e, c, b, a, called, rn);
         break;
     }
@@ -774,6 +844,21 @@ int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.actions = actions; c.flags = JSS_ROLLOUT_AUTORESET;
     return run(c, kStep);
+}
+
+int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
+                    const JssOut *out, void *) {
+    int rc = check_args(desc, state, out, true);
+    if (rc) return rc;
+    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
+    if (lg->row != 0 && lg->row < (int64_t)desc->jmax + 1) return JSS_E_SHAPE;
+    if (lg->row > (1 << 24)) return JSS_E_SHAPE;
+    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
+    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    Call c;
+    c.d = *desc; c.s = *state; c.o = *out; c.lg = *lg; c.seed = seed; c.flags = flags & JSS_ROLLOUT_AUTORESET;
+    if (c.lg.row == 0) c.lg.row = desc->jmax + 1;
+    return run(c, kLogits);
 }
 
 int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which, int32_t *hole, const JssOut *out, void *) {

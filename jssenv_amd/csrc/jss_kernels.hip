@@ -622,6 +622,23 @@ int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t
     return launch<kStep>(p, stream);
 }
 
+// jss_step + the masked categorical draw from the caller's logits in one launch (kLogits: every kernel family kStep has, one
+// env per wavefront at a time -- two_per_wave stays off)
+int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
+                    const JssOut *out, void *stream) {
+    int rc = check_args(desc, state, out, true);
+    if (rc) return rc;
+    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
+    if (lg->row != 0 && lg->row < (int64_t)desc->jmax + 1) return JSS_E_SHAPE;
+    if (lg->row > (1 << 24)) return JSS_E_SHAPE;                         // (lane offsets are 32-bit)
+    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
+    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    Params p = {};
+    p.d = *desc; p.s = *state; p.o = *out; p.lg = *lg; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
+    if (p.lg.row == 0) p.lg.row = desc->jmax + 1;
+    return launch<kLogits>(p, stream);
+}
+
 int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which, int32_t *hole, const JssOut *out,
                 void *stream) {
     int rc = check_args(desc, state, out, true);

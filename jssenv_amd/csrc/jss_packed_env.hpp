@@ -119,6 +119,13 @@ __device__ __forceinline__ int grp_sum(int v) {
     return v;
 }
 
+template <int G>
+__device__ __forceinline__ float grp_fsum(float v) {
+    v = row_fsum(v);
+    if (G == 32) v += as_float(__builtin_amdgcn_ds_swizzle(as_int(v), 0x401F));
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------
 // reset(): jss_env.py:145-181 (registers only; `on` = groups being reset)
 // ---------------------------------------------------------------------------------------
@@ -516,6 +523,76 @@ __device__ __forceinline__ int p_select(const PEnv<G> &e, const PCtx<G, TAB> &c,
         }
     }
     return n == 0 ? -1 : a;
+}
+
+// ---------------------------------------------------------------------------------------
+// jss_step_logits (kLogits): the action drawn from the caller's logits (include/jss_hip.h).  Lane gl holds entry gl of its
+// env's row: job gl, or NOPE on the spare lane gl == J when J < G; an env whose J fills the group (J == G) has NOPE's entry
+// behind the lanes, at index G, and every lane of the group folds it in after the group reduction.
+// ---------------------------------------------------------------------------------------
+struct PLogits {
+    int v;      // bits of entry gl (float32, or bfloat16 in the low half)
+    int nope;   // bits of entry G (rows wider than the group only)
+};
+// issued with the state loads: the addresses depend on nothing but the env index and the lane (entry gl clamped into the row)
+template <int G, int TAB>
+__device__ __forceinline__ PLogits p_issue_logits(const PCtx<G, TAB> &c, const Params &p) {
+    PLogits r;
+    const unsigned row = (unsigned)p.lg.row, at = c.rel * row;
+    const unsigned idx = (unsigned)c.gl <= (unsigned)p.d.jmax ? (unsigned)c.gl : 0u;
+    const size_t fe = (size_t)c.first_env * p.lg.row;
+    if (p.lg.dtype == JSS_LOGITS_BF16) {
+        const uint16_t *lb = static_cast<const uint16_t *>(p.lg.logits) + fe;
+        r.v = ld_off<uint16_t>(lb, (at + idx) * 2u);
+        r.nope = p.d.jmax >= G ? ld_off<uint16_t>(lb, (at + G) * 2u) : 0;
+    } else {
+        const int32_t *lb = static_cast<const int32_t *>(p.lg.logits) + fe;
+        r.v = ld_off<int>(lb, (at + idx) * 4u);
+        r.nope = p.d.jmax >= G ? ld_off<int>(lb, (at + G) * 4u) : 0;
+    }
+    return r;
+}
+
+// The action of my env (group-uniform): Gumbel-max over the legal entries, JSS_ACTION_SKIP when nothing is legal, a_in
+// (JSS_ACTION_RESET: autoreset of a done env) untouched; writes action / logp / entropy and flags JSS_ERR_BAD_LOGITS.
+// Branch-free across groups: every lane takes part in the reductions, the result is kept where it applies.
+template <int G, int TAB>
+__device__ __forceinline__ int p_logits_pick(PEnv<G> &e, const PCtx<G, TAB> &c, const Params &p, uint32_t episode, uint32_t step,
+                                             int a_in, const PLogits &lr) {
+    const size_t fe = (size_t)c.first_env;
+    const uint64_t env_id = (uint64_t)(p.d.env_ids ? ld_off<int64_t>(p.d.env_ids + fe, c.rel * 8u)
+                                                   : p.d.env_id_base + (int64_t)(fe + c.rel));
+    const uint32_t r = rng_u32(p.seed ^ kLogitsSeedXor, env_id, episode, step);
+    const float T = p.lg.temperature;
+    const int dtype = p.lg.dtype;
+    const bool part = c.alive && ((c.jvalid && e.legal) || (c.gl == c.J && e.noop != 0));
+    const LgEntry en = lg_entry(logit_of(lr.v, dtype), part, c.gl, r, T);
+    LgEntry np = {kOrdNone, kOrdNone, 0.f, false};
+    if (c.J == G) np = lg_entry(logit_of(lr.nope, dtype), c.alive && e.noop != 0, G, r, T);   // (group-uniform)
+    const int best = grp_max<G>(en.skey);
+    const uint32_t hit = grp_ballot<G>(part && en.skey == best, c.gbase);
+    const bool nope_wins = np.skey > best;                               // index G: it wins ties against nobody
+    const int a = nope_wins ? G : hit ? __ffs(hit) - 1 : -1;
+    const float m = ord_float(imax(grp_max<G>(en.xkey), np.xkey));
+    float w, wx, nw, nwx;
+    lg_terms(en, m, w, wx);
+    lg_terms(np, m, nw, nwx);
+    const float s = grp_fsum<G>(w) + nw, sx = grp_fsum<G>(wx) + nwx;
+    const float xr = as_float(grp_read<G>(as_int(en.x), a, c.gbase));   // (every lane: a collective, outside the choice)
+    const float xa = nope_wins ? np.x : xr;
+    const bool bad = grp_any<G>(en.bad, c.gbase) || np.bad;
+    float logp, entropy;
+    lg_finish(m, s, sx, xa, logp, entropy);
+    const bool take = a_in != JSS_ACTION_RESET && a >= 0;
+    if (!take) logp = entropy = 0.f;
+    if (take && bad) e.err |= JSS_ERR_BAD_LOGITS;
+    const int act = take ? a : a_in;
+    if (c.alive && c.gl == 0) {
+        st_off<int>(p.lg.action + fe, c.rel * 4u, act);
+        if (p.lg.logp) st_off<float>(p.lg.logp + fe, c.rel * 4u, logp);
+        if (p.lg.entropy) st_off<float>(p.lg.entropy + fe, c.rel * 4u, entropy);
+    }
+    return act;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -962,7 +1039,7 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
                 st_off<uint8_t>(p.o.done + fe, c.rel, 0);
             }
         }
-    } else if (MODE == kStep) {
+    } else if (MODE == kStep || MODE == kLogits) {                      // (kLogits: a_in = the action drawn, p_logits_pick)
         int rn;
         bool called;
         fresh = p_step_call<G, TAB, false>(e, hd, c, p, a_in, mvtab, rn, called);
@@ -1114,9 +1191,14 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     int a_in = JSS_ACTION_SKIP;
     bool selected = true;
     int4 hx = make_int4(0, 0, 0, 0);
+    PLogits lr = {0, 0};
     c.tid = 0;
     if (!wave_dead) {
         raw = p_issue_loads<G, TAB>(c, p);
+        if constexpr (MODE == kLogits) {
+            lr = p_issue_logits<G, TAB>(c, p);
+            if ((p.flags & JSS_ROLLOUT_AUTORESET) && ld_off<uint8_t>(p.o.done + fe, c.rel) != 0) a_in = JSS_ACTION_RESET;
+        }
         if (MODE == kStep) {
             a_in = ld_off<int>(p.actions + fe, c.rel * 4u);
             // jss_step_autoreset: an env that reported done on the previous call is reset instead of stepped
@@ -1172,6 +1254,7 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     // an env that was never reset (episode counter 0: every reset bumps it) is left alone by the step-type calls, like
     // the one-wavefront-per-env kernel and the host twin do (J == 0 in its constants record): no stores, no counters
     if (MODE != kReset && hd.episode == 0) c.alive = false;
+    if constexpr (MODE == kLogits) a_in = p_logits_pick(e, c, p, (uint32_t)hd.episode, (uint32_t)hd.step, a_in, lr);
     int a_sched;
     bool restarted;
 #ifdef JSS_COUNTERS_PLAIN
@@ -1183,7 +1266,7 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     // (by cause with per-env tables only: +1.6 % on 15x15 x 65 536, full records 67 -> 61 VGPRs = 8 wavefronts per SIMD; on a
     //  shared table -- 16-byte records, four words to compare -- it measured 0..2 % SLOWER: profiles/r06_misc/stores_by_cause_ab.txt)
     constexpr int kDiffStores = (MODE == kRollout || MODE == kTraj || MODE == kSteps) ? kStoreAll
-                                : ((MODE == kStep || MODE == kRollout1) && tab_global(TAB)) ? JSS_ONE_STEP_STORES : kStoreCompare;
+                                : ((MODE == kStep || MODE == kLogits || MODE == kRollout1) && tab_global(TAB)) ? JSS_ONE_STEP_STORES : kStoreCompare;
     p_store<G, TAB, kDiffStores>(e, c, p, hd, raw, fresh, restarted || e.t != raw.h.x, a_sched);
     p_store_mask<G, TAB, false, PADDED>(e, c, p, p.o.action_mask + fe * (p.d.jmax + 1));
     if (!JSS_ABLATED(p, JSS_ABLATE_OBS))
@@ -1194,7 +1277,7 @@ template <int G, int MODE, int TAB>
 __global__ __launch_bounds__(kBlock, (MODE == kTraj || MODE == kSteps) ? (tab_global(TAB) && !tab_medium(TAB) ? JSS_PTRAJ_GLOBAL_MIN_BLOCKS : JSS_PTRAJ_LDS_MIN_BLOCKS)
                                      : MODE == kRollout ? (tab_global(TAB) ? 4 : 5)
                                      : (tab_medium(TAB) && MODE == kRollout1) ? JSS_PACKED_MEDIUM_MIN_BLOCKS
-                                     : ((tab_global(TAB) && (MODE == kStep || MODE == kRollout1)) ? JSS_PACKED_GLOBAL_MIN_BLOCKS : 8))
+                                     : ((tab_global(TAB) && (MODE == kStep || MODE == kLogits || MODE == kRollout1)) ? JSS_PACKED_GLOBAL_MIN_BLOCKS : 8))
 void jss_packed_kernel(Params p_arg) {
     HIP_DYNAMIC_SHARED(int32_t, lds)
     // By value for the one-step kernels: they fit their SGPR budget, and with every argument loaded up front -- behind the state

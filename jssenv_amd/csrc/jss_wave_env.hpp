@@ -570,6 +570,99 @@ __device__ __forceinline__ int select_action(const Env<JPL> &e, const Ctx &c, co
 }
 
 // ---------------------------------------------------------------------------------------
+// jss_step_logits (kLogits): the action drawn from the caller's logits (include/jss_hip.h).  Lane l holds entries l and
+// 64 + l (JPL slots, like the jobs); NOPE's entry (index J) sits on lane J % 64 of slot J / 64 -- unless J fills every slot
+// (J == 64 JPL), then it is loaded as one more wave-uniform value and folded in after the reduction.
+// ---------------------------------------------------------------------------------------
+template <int JPL>
+struct WLogits {
+    int v[JPL];   // bits of entry s * 64 + lane (float32, or bfloat16 in the low half)
+    int nope;     // bits of entry 64 JPL (rows that wide only)
+};
+// issued with the state loads: the addresses depend on nothing but the env index and the lane (clamped into the row)
+template <int JPL>
+__device__ __forceinline__ WLogits<JPL> wave_issue_logits(const Params &p, int b, int lane) {
+    WLogits<JPL> r;
+    const size_t base = (size_t)b * p.lg.row;
+    const bool bf16 = p.lg.dtype == JSS_LOGITS_BF16;
+    const uint16_t *lh = static_cast<const uint16_t *>(p.lg.logits) + base;
+    const int32_t *lw = static_cast<const int32_t *>(p.lg.logits) + base;
+#pragma unroll
+    for (int s = 0; s < JPL; ++s) {
+        const unsigned j = (unsigned)(s * kWave + lane), idx = j <= (unsigned)p.d.jmax ? j : 0u;
+        r.v[s] = bf16 ? (int)ld_off<uint16_t>(lh, idx * 2u) : ld_off<int>(lw, idx * 4u);
+    }
+    const unsigned jn = JPL * kWave;
+    r.nope = p.d.jmax >= (int)jn ? (bf16 ? (int)ld_off<uint16_t>(lh, jn * 2u) : ld_off<int>(lw, jn * 4u)) : 0;
+    return r;
+}
+
+// float sum over the wave: four row sums combined on the scalar unit
+__device__ __forceinline__ float wave_fsum(float v) {
+    v = row_fsum(v);
+    return (as_float(__builtin_amdgcn_readlane(as_int(v), 0)) + as_float(__builtin_amdgcn_readlane(as_int(v), 16))) +
+           (as_float(__builtin_amdgcn_readlane(as_int(v), 32)) + as_float(__builtin_amdgcn_readlane(as_int(v), 48)));
+}
+
+// The action (wave-uniform): Gumbel-max over the legal entries, JSS_ACTION_SKIP when nothing is legal; logp / entropy out,
+// JSS_ERR_BAD_LOGITS flagged
+template <int JPL>
+__device__ __forceinline__ int wave_logits_pick(Env<JPL> &e, const Ctx &c, const Params &p, uint32_t episode,
+                                                uint32_t step, const WLogits<JPL> &lr, float &logp, float &entropy) {
+    logp = entropy = 0.f;
+    if (!any_legal(e) && !e.noop) return JSS_ACTION_SKIP;
+    const uint64_t env_id = (uint64_t)(p.d.env_ids ? p.d.env_ids[c.b] : p.d.env_id_base + c.b);
+    const uint32_t r = rng_u32(p.seed ^ kLogitsSeedXor, env_id, episode, step);
+    const float T = p.lg.temperature;
+    const int dtype = p.lg.dtype;
+    LgEntry en[JPL];
+    bool part[JPL];
+    int bs = kOrdNone, bx = kOrdNone;
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < JPL; ++s) {
+        const int j = s * kWave + c.lane;
+        part[s] = ((e.legal[s] >> c.lane) & 1) || (j == c.J && e.noop != 0);
+        en[s] = lg_entry(logit_of(lr.v[s], dtype), part[s], j, r, T);
+        bs = imax(bs, en[s].skey);
+        bx = imax(bx, en[s].xkey);
+        bad = bad || en[s].bad;
+    }
+    LgEntry np = {kOrdNone, kOrdNone, 0.f, false};
+    if (c.J == JPL * kWave) np = lg_entry(logit_of(lr.nope, dtype), e.noop != 0, c.J, r, T);   // (wave-uniform)
+    const int best = wave_max(bs);
+    int a = -1;
+#pragma unroll
+    for (int s = 0; s < JPL; ++s) {                                      // the lowest index wins ties
+        const uint64_t hit = __ballot(part[s] && en[s].skey == best);
+        if (a < 0 && hit) a = s * kWave + __ffsll((unsigned long long)hit) - 1;
+    }
+    const bool nope_wins = np.skey > best;
+    if (nope_wins) a = c.J;
+    const float m = ord_float(imax(wave_max(bx), np.xkey));
+    float w = 0.f, wx = 0.f;
+#pragma unroll
+    for (int s = 0; s < JPL; ++s) {
+        float ws, wxs;
+        lg_terms(en[s], m, ws, wxs);
+        w += ws;
+        wx += wxs;
+    }
+    float nw, nwx;
+    lg_terms(np, m, nw, nwx);
+    const float sum = wave_fsum(w) + nw, sumx = wave_fsum(wx) + nwx;
+    float xa = np.x;
+    if (!nope_wins) {
+        int xs = as_int(en[0].x);
+        if (JPL > 1 && (a >> 6)) xs = as_int(en[JPL - 1].x);
+        xa = as_float(__builtin_amdgcn_readlane(xs, a & 63));
+    }
+    if (__ballot(bad) != 0 || np.bad) e.err |= JSS_ERR_BAD_LOGITS;
+    lg_finish(m, sum, sumx, xa, logp, entropy);
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------
 // HBM <-> registers.  One 32-byte record per job (two dwordx4 per lane), a 16-byte header + 48 bytes of constants per env.
 // The env index is wave-uniform, so every base is an SGPR pair and the lane offset 32 bits.
 // ---------------------------------------------------------------------------------------
@@ -1034,9 +1127,11 @@ __device__ __forceinline__ void loads_landed(const RawEnv<JPL> &r) {
 // the claim, then the stores, under `live` again: with an early return in front of it the waits of the two paths merge at the
 // join and the second env starts with an s_waitcnt for the first env's stores after all.
 // (NEXT = false, one env per wavefront: `live` false returns on the spot -- the form, and the code, these kernels always had)
+// (lgr: kLogits only, the caller's logits as loaded by wave_issue_logits)
 template <int JPL, int MODE, int TAB, bool NEXT = false>
 __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const HeaderWords &h, RawEnv<JPL> raw, int a_in,
-                                            const int32_t *lds, float *scratch, const RawEnv<JPL> *next = nullptr) {
+                                            const int32_t *lds, float *scratch, const RawEnv<JPL> *next = nullptr,
+                                            const WLogits<JPL> *lgr = nullptr) {
     const int b = c.b, lane = c.lane;
     Header hd = {0, 0};
     Env<JPL> e = {};
@@ -1082,6 +1177,16 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
     } else if (MODE == kStep) {                                          // (JSS_ACTION_RESET never gets here: jss_kernel)
         sr = step_compute<JPL, TAB, false, false>(e, hd, c, p, lds, a_in);
         a_sched = a_in;
+    } else if constexpr (MODE == kLogits) {                             // (JSS_ACTION_RESET never gets here either)
+        float logp, entropy;
+        const int a = wave_logits_pick(e, c, p, (uint32_t)hd.episode, (uint32_t)hd.step, *lgr, logp, entropy);
+        if (lane == 0) {
+            p.lg.action[b] = a;
+            if (p.lg.logp) p.lg.logp[b] = logp;
+            if (p.lg.entropy) p.lg.entropy[b] = entropy;
+        }
+        sr = step_compute<JPL, TAB, false, false>(e, hd, c, p, lds, a);
+        a_sched = a;
     } else if (MODE == kSteps) {
         // n_iter x jss_step with the actions given up front: the state stays in registers, every step optionally recorded
         for (int it = 0; it < p.n_iter; ++it) {
@@ -1158,7 +1263,7 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
     if (NEXT) loads_landed(*next);
     if (!live) return;
     // ---- the epilogue: the env's scalar outputs, its state, mask and observation ----
-    if (MODE == kStep) {
+    if (MODE == kStep || MODE == kLogits) {
         step_outputs<JPL, false>(e, c, p, sr);
     } else if (MODE == kRollout || MODE == kRollout1 || MODE == kTraj) {
         if (lane == 0) {
@@ -1175,7 +1280,7 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
     //  +3 %; on a shared table -- four words per record to compare -- by cause measured 1-2 % slower:
     //  profiles/r06_misc/stores_by_cause_ab.txt)
     constexpr int kDiffStores = (MODE == kRollout || MODE == kSteps || (MODE == kTraj && JPL == 2)) ? kStoreAll
-                                : ((MODE == kStep || MODE == kRollout1) && tab_global(TAB)) ? JSS_ONE_STEP_STORES : kStoreCompare;
+                                : ((MODE == kStep || MODE == kLogits || MODE == kRollout1) && tab_global(TAB)) ? JSS_ONE_STEP_STORES : kStoreCompare;
     store_env<JPL, TAB, kDiffStores>(e, c, p, hd, raw, fresh, restarted || e.t != __builtin_amdgcn_readfirstlane(h.clock), a_sched);
     store_mask(e, c, p.o.action_mask + (size_t)b * (p.d.jmax + 1), p.d.jmax);
     JSS_STAMP(p, b, 5, e.t);
@@ -1189,7 +1294,12 @@ __device__ __forceinline__ void wave_main(const Params &p, Ctx &c, const HeaderW
                                           const int32_t *lds, float *scratch) {
     RawEnv<JPL> raw;
     if (MODE != kReset) raw = wave_issue<JPL, TAB>(p, c.b, c.lane, h, ragged);   // (a reset reads nothing)
-    wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch);
+    if constexpr (MODE == kLogits) {
+        const WLogits<JPL> lr = wave_issue_logits<JPL>(p, c.b, c.lane);
+        wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch, nullptr, &lr);
+    } else {
+        wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1220,7 +1330,7 @@ __device__ __forceinline__ void wave_main(const Params &p, Ctx &c, const HeaderW
 constexpr int wave_min_blocks(int jpl, int mode, int tab) {
     return mode == kTraj ? (jpl == 2 ? JSS_TRAJ2_MIN_BLOCKS : JSS_TRAJ1_MIN_BLOCKS)
          : mode == kRollout ? (jpl == 2 ? 5 : 7)
-         : mode == kStep ? (jpl == 2 ? 5 : 8)
+         : (mode == kStep || mode == kLogits) ? (jpl == 2 ? 5 : 8)
          : mode == kSteps ? (jpl == 2 ? 4 : 6)
          : mode == kRollout1 ? (jpl == 2 ? (tab_medium(tab) ? 6 : JSS_WAVE2_MIN_BLOCKS) : JSS_WAVE_MIN_BLOCKS)
          : (jpl == 2 ? 7 : 8);
@@ -1249,6 +1359,9 @@ __device__ __forceinline__ void wave_block(const Params &p, int block, int32_t *
         // jss_step_autoreset: an env that reported done on the previous call is reset instead of stepped
         if ((p.flags & JSS_ROLLOUT_AUTORESET) && __builtin_amdgcn_readfirstlane((int)p.o.done[b]) != 0) a_in = JSS_ACTION_RESET;
     }
+    if constexpr (MODE == kLogits) {                                      // jss_step_logits with autoreset: the same
+        if ((p.flags & JSS_ROLLOUT_AUTORESET) && __builtin_amdgcn_readfirstlane((int)p.o.done[b]) != 0) a_in = JSS_ACTION_RESET;
+    }
     bool selected = true;
     if ((MODE == kReset || MODE == kAdvance) && p.which) selected = __builtin_amdgcn_readfirstlane((int)p.which[b]) != 0;
     if (tab_in_lds(TAB)) {                                                // one instance for the whole batch: its op table -> LDS
@@ -1261,12 +1374,19 @@ __device__ __forceinline__ void wave_block(const Params &p, int block, int32_t *
         const int tid = tab_in_lds(TAB) ? 0 : __builtin_amdgcn_readfirstlane(p.d.table_of_env ? p.d.table_of_env[b] : b);
         ctx_from_instance(c, p, tid);
         wave_main<JPL, MODE, TAB>(p, c, h, ragged, a_in, lds, scratch);   // full width: a reset writes every row of the padded block
-    } else if (MODE == kStep && a_in == JSS_ACTION_RESET) {
+    } else if ((MODE == kStep || MODE == kLogits) && a_in == JSS_ACTION_RESET) {
         // jss_step's "reset this env instead of stepping it" IS a reset: nothing of the old state is needed but the episode
         // counter, and the env may have been handed another (wider) instance since (table_of_env) -- the reset body, full width
         if (__builtin_amdgcn_readfirstlane(h.J) == 0) return;            // never reset: left alone, like by every step-type call
         const int tid = tab_in_lds(TAB) ? 0 : __builtin_amdgcn_readfirstlane(p.d.table_of_env ? p.d.table_of_env[b] : h.tid);
         ctx_from_instance(c, p, tid);
+        if constexpr (MODE == kLogits) {
+            if (lane == 0) {
+                p.lg.action[b] = JSS_ACTION_RESET;
+                if (p.lg.logp) p.lg.logp[b] = 0.f;
+                if (p.lg.entropy) p.lg.entropy[b] = 0.f;
+            }
+        }
         wave_main<JPL, kReset, TAB>(p, c, h, ragged, a_in, lds, scratch);
     } else {
         // (J == 64 stays on the full-width body: the NOPE flag of its mask row lives at index 64, slot 1's first lane)

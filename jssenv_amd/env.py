@@ -152,7 +152,8 @@ class BatchedJssEnv:
                      ("action_mask", (B, J + 1), "uint8"),
                      ("reward", (B,), "float32"), ("done", (B,), "uint8"), ("makespan", (B,), "int32"),
                      ("_actions_out", (B,), "int32"), ("_hole", (B,), "int32"), ("_act_buf", (B,), "int32"),
-                     ("_act_in", (B,), "int32"), ("_which_in", (B,), "uint8")]
+                     ("_act_in", (B,), "int32"), ("_which_in", (B,), "uint8"),
+                     ("_lg_action", (B,), "int32"), ("_lg_logp", (B,), "float32"), ("_lg_entropy", (B,), "float32")]
             if self.no_clocks:
                 specs = [sp for sp in specs if sp[0] != "machine_state"]
             self._layout, off = {}, 0
@@ -418,6 +419,80 @@ class BatchedJssEnv:
                                                      int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()),
                            "jss_policy")
         return self._actions_out
+
+    def _logits_arg(self, logits):
+        """(pointer, row stride, JSS_LOGITS_* dtype, the object to keep alive) of a (B, >= jmax + 1) float32 / bfloat16
+        array whose last dim is contiguous: a tensor on the env's device (host backends: a CPU tensor or a NumPy array);
+        anything else is copied to float32 first, a view whose rows lie closer than jmax + 1 elements (a broadcast row) into
+        whole rows."""
+        be, B, J = self.backend, self.batch, self.jmax
+        on_gpu = hasattr(be, "torch")                 # HipBackend: torch tensors on the device; host backends: host memory
+        if hasattr(logits, "data_ptr"):               # a torch tensor
+            if bool(logits.is_cuda) != on_gpu:
+                logits = logits.to(be.device) if on_gpu else logits.cpu()
+            if str(logits.dtype) not in ("torch.float32", "torch.bfloat16"):
+                logits = logits.float()
+        elif on_gpu or np.asarray(logits).dtype != np.float32:
+            logits = be.as_device(logits, "float32")
+        shape = tuple(logits.shape)
+        if len(shape) != 2 or shape[0] != B or shape[1] < J + 1:
+            raise ValueError(f"expected logits of shape ({B}, >= {J + 1}), got {shape}")
+        # rows closer together than jmax + 1 elements (a broadcast row: stride 0; overlapping or reversed rows) are not a layout
+        # the library can take -- JssLogits.row 0 would even mean "jmax + 1" -- so such a view is copied into whole rows first
+        if hasattr(logits, "data_ptr"):
+            if logits.stride(1) != 1:
+                raise ValueError("the last dim of logits must be contiguous")
+            if logits.stride(0) < J + 1:
+                logits = logits.new_empty(logits.shape).copy_(logits)
+            ptr, row, bf16 = logits.data_ptr(), logits.stride(0), str(logits.dtype) == "torch.bfloat16"
+        else:
+            if logits.strides[1] != 4:
+                raise ValueError("the last dim of logits must be contiguous")
+            if logits.strides[0] < 4 * (J + 1) or logits.strides[0] % 4:
+                logits = np.array(logits, dtype=np.float32, order="C", copy=True)
+            ptr, row, bf16 = logits.ctypes.data, logits.strides[0] // 4, False
+        assert row >= J + 1, row
+        return ptr, int(row), _abi.LOGITS_BF16 if bf16 else _abi.LOGITS_F32, logits
+
+    def step_logits(self, logits, temperature: float = 1.0, seed: Optional[int] = None, autoreset: bool = False,
+                    logp: bool = True, entropy: bool = False):
+        """step() with the action drawn on the device from the caller's logits (``jss_step_logits``): per env a masked
+        categorical draw from softmax(logits / temperature) over the legal actions (jobs whose mask bit is set, NOPE at index
+        J(env) when it is legal; Gumbel-max, keyed like the random policy by (seed, env id, episode, step)), its
+        log-probability and the entropy of the masked distribution, and the step itself -- one launch, the env state ends
+        bit-identical to ``step(info["action"])``.  ``temperature=0``: greedy (argmax, lowest index on ties; logp / entropy
+        for T = 1).  ``logits``: (B, >= jmax + 1) float32 or bfloat16 on the env's device, last dim contiguous; entries behind
+        J(env) are never read as actions.  ``seed=None``: ``self.seed``.  ``autoreset=True``: an env that reported done is
+        reset instead (action -2, logp 0, entropy 0); an env with no legal action is left alone (action -1, logp 0).
+
+        Returns (obs, reward, done, False, info) with info = {"action": (B,) int32[, "logp": (B,) float32][, "entropy"]} (as
+        asked for by ``logp`` / ``entropy``): the env's own buffers, overwritten by the next call."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before step_logits()")
+        if not float(temperature) >= 0.0:
+            raise ValueError("temperature must be >= 0")
+        be = self.backend
+        self._refs()                                  # (refuses while a session is open)
+        sd, flags = self.seed if seed is None else int(seed), _abi.ROLLOUT_AUTORESET if autoreset else 0
+        with be.on_device():
+            ptr, row, dtype, keep = self._logits_arg(logits)
+        item = 2 if dtype == _abi.LOGITS_BF16 else 4
+        outs = (self._lg_action, self._lg_logp if logp else None, self._lg_entropy if entropy else None)
+        lgs = []
+
+        def call(d, s, o, first, stream):             # (by shape class: one launch per range, every pointer at its first env)
+            at = lambda t, size: be.ptr(t) + first * size if t is not None else None      # noqa: E731
+            lgs.append(_abi.JssLogits(ptr + first * row * item, row, dtype, float(temperature),
+                                      at(outs[0], 4), at(outs[1], 4), at(outs[2], 4)))
+            return be.lib.jss_step_logits(d, s, C.byref(lgs[-1]), sd, flags, o, stream)
+        self._over_ranges(call, "jss_step_logits")
+        self._logits_keep = keep                      # alive until the launch has read it
+        info = {"action": self._lg_action}
+        if logp:
+            info["logp"] = self._lg_logp
+        if entropy:
+            info["entropy"] = self._lg_entropy
+        return self._obs(), self.reward, self.done, False, info
 
     def rollout(self, kind: Union[str, int] = "random", n_iter: int = 1, seed: Optional[int] = None,
                 autoreset: bool = True, explore: float = 0.0):

@@ -72,6 +72,16 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         truncations = terminations & False
         return self._obs(), self._out(reward), self._out(terminations), self._out(truncations), {}
 
+    def step_logits(self, logits, temperature: float = 1.0):
+        """``step`` with the actions drawn on the device from the policy's (num_envs, J + 1) logits, masked by the action mask
+        (BatchedJssEnv.step_logits, autoreset as ``step``).  infos = {"action", "logp", "entropy"} (num_envs,) each: the
+        action taken (-2 = the env was reset), its log-probability and the entropy of the masked distribution."""
+        _, reward, done, _, info = self.env.step_logits(logits, temperature=temperature, autoreset=True, logp=True, entropy=True)
+        terminations = done != 0
+        truncations = terminations & False
+        infos = {k: self._out(v) for k, v in info.items()}
+        return self._obs(), self._out(reward), self._out(terminations), self._out(truncations), infos
+
     def sample_actions(self, kind="random", explore: float = 0.0):
         """Per-env actions from the on-device selectors (random masked, FIFO, SPT, ...)."""
         return self.env.policy(kind, explore=explore)
