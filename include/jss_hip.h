@@ -84,7 +84,7 @@
 extern "C" {
 #endif
 
-#define JSS_ABI_VERSION 11
+#define JSS_ABI_VERSION 12
 
 #define JSS_MAX_JOBS 128
 #define JSS_MAX_MACHINES 64
@@ -523,6 +523,17 @@ typedef struct JssLogits {
 } JssLogits;
 int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
                     const JssOut *out, void *stream);
+/* jss_multi_step_logits = jss_step_logits over several env sets, as jss_multi_step is jss_step (ABI v12): set i is
+ * stepped from its own lgs[i] (logits, row, dtype, temperature, outputs) exactly as jss_step_logits(descs[i], states[i],
+ * lgs[i], seed, flags, outs[i]) steps it -- the same draws, keyed by the global env id (JssDesc.env_ids or env_id_base + i),
+ * whichever body runs them.  State, outputs and the actions are bit-identical to the single-set call; logp / entropy agree
+ * with it to float32 rounding (the grid may reduce an env's entries over a 16- or 32-lane group where the single-set call
+ * on padded rows uses a wavefront).  One fused grid for 2 to 6 sets with per-env tables (as jss_multi_step), otherwise one
+ * plain launch per set on `stream`.  flags: JSS_ROLLOUT_AUTORESET only.  Errors (nothing is launched then): those of
+ * jss_multi_step's sets, JSS_E_NULL for a NULL lgs or a NULL entry, and every lgs[i] checked as jss_step_logits checks lg
+ * (a row outside [jmax + 1, 2^24] of ITS set: JSS_E_SHAPE; a bad dtype or temperature: JSS_E_KIND). */
+int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
+                          const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream);
 
 #ifdef JSS_PROFILING
 /* Instrumented builds only (tools/build_instrumented.py compiles with -DJSS_PROFILING; the shipped library does

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 STATE_LAYOUT = 7     # version of the state tensors' layout (checkpoints): unchanged since ABI v7
 MAX_JOBS, MAX_MACHINES = 128, 64
 F_TODO, F_CUR, F_LEFT, F_PERF, F_IDLE, F_IDLE_LAST, F_F4, F_NEXT, NF = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -65,7 +65,8 @@ MAX_SUB_BATCHES = 16
 SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "jss_step", "jss_advance", "jss_policy",
            "jss_rollout", "jss_rollout_steps", "jss_rollout_steps_multi", "jss_trajectory", "jss_sync_check",
            "jss_step_autoreset", "jss_policy_step_steps", "jss_steps", "jss_session_open", "jss_session_post", "jss_session_wait", "jss_session_step", "jss_session_close",
-           "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits")
+           "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits",
+           "jss_multi_step_logits")
 
 _p = C.c_void_p
 
@@ -153,6 +154,8 @@ def bind(lib):
     lib.jss_session_step.restype, lib.jss_session_step.argtypes = C.c_int, [D, SS, _p, C.c_int32, _p]
     lib.jss_step_logits.restype = C.c_int
     lib.jss_step_logits.argtypes = [D, S, C.POINTER(JssLogits), C.c_uint64, C.c_int32, O, _p]
+    lib.jss_multi_step_logits.restype = C.c_int
+    lib.jss_multi_step_logits.argtypes = [C.c_int32, PD, PS, C.POINTER(C.POINTER(JssLogits)), C.c_uint64, C.c_int32, PO, _p]
     if lib.jss_abi_version() != ABI_VERSION:
         raise RuntimeError(f"library ABI {lib.jss_abi_version()} != expected {ABI_VERSION}")
     return lib

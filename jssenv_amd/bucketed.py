@@ -11,7 +11,7 @@ instance runs on the two-jobs-per-lane wave kernel with 85 % of its lanes idle.
     class 3: J <= 128     -> one wavefront per env, two jobs per lane
 
 each backed by its own compactly padded ``BatchedJssEnv`` (own tensors).  Every call --
-``reset``, ``policy``, ``step``, ``rollout_steps`` -- is ONE launch over all classes
+``reset``, ``policy``, ``step``, ``step_logits``, ``rollout_steps`` -- is ONE launch over all classes
 (``jss_multi_*``, include/jss_hip.h: a workgroup of the grid finds its class by its index and
 runs that class's body), on the caller's stream: no side streams, no per-class launches whose
 overlap depends on how the runtime deals streams onto hardware queues.  Env ``i`` of the
@@ -186,6 +186,29 @@ class BucketedJssEnv:
                                        _abi.ROLLOUT_AUTORESET if autoreset else 0, be.stream())
         _abi.check(be.lib, rc, "jss_multi_step")
         return {k: (b._obs(), b.reward, b.done, False, {}) for k, b in each}
+
+    def step_logits(self, logits_per_bucket, temperature: float = 1.0, seed: Optional[int] = None, autoreset: bool = False,
+                    logp: bool = True, entropy: bool = False):
+        """BatchedJssEnv.step_logits of every env, one launch over all classes (jss_multi_step_logits): logits_per_bucket =
+        {class: (B_class, >= jmax_class + 1) float32 / bfloat16 logits}, each bucket's rows in its own slot order and laid out
+        like its action mask.  The draws are keyed by the global env id, as in the padded batch.  Returns {class: (obs, reward,
+        done, False, info)} with info as BatchedJssEnv.step_logits gives it (each bucket's own buffers)."""
+        self._check_reset("step_logits")
+        if not float(temperature) >= 0.0:
+            raise ValueError("temperature must be >= 0")
+        be = self._backend
+        each = self._each()
+        flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
+        with be.on_device():
+            args = [b._logits_arg(logits_per_bucket[k]) for k, b in each]
+            lgs = [b._logits_struct(a, temperature, logp, entropy) for (_, b), a in zip(each, args)]
+            ptrs = (C.POINTER(_abi.JssLogits) * self._n_sets)(*[C.pointer(x) for x in lgs])
+            rc = be.lib.jss_multi_step_logits(self._n_sets, self._sets[0], self._sets[1], ptrs, self._seed(seed), flags,
+                                              self._sets[2], be.stream())
+        _abi.check(be.lib, rc, "jss_multi_step_logits")
+        for (_, b), a in zip(each, args):
+            b._logits_keep = a[3]                    # alive until the launch has read it
+        return {k: (b._obs(), b.reward, b.done, False, b._logits_info(logp, entropy)) for k, b in each}
 
     def synchronize(self):
         for _, b in self._each():

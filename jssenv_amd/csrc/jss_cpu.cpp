@@ -793,6 +793,16 @@ int check_kind(const JssDesc *d, int kind_arg, bool f64_ok = false) {
     return 0;
 }
 
+// jss_step_logits' checks of a JssLogits against its set's description
+int check_logits(const JssDesc *d, const JssLogits *lg) {
+    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
+    if (lg->row != 0 && lg->row < (int64_t)d->jmax + 1) return JSS_E_SHAPE;
+    if (lg->row > (1 << 24)) return JSS_E_SHAPE;
+    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
+    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -850,11 +860,7 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
                     const JssOut *out, void *) {
     int rc = check_args(desc, state, out, true);
     if (rc) return rc;
-    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
-    if (lg->row != 0 && lg->row < (int64_t)desc->jmax + 1) return JSS_E_SHAPE;
-    if (lg->row > (1 << 24)) return JSS_E_SHAPE;
-    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
-    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    if ((rc = check_logits(desc, lg))) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.lg = *lg; c.seed = seed; c.flags = flags & JSS_ROLLOUT_AUTORESET;
     if (c.lg.row == 0) c.lg.row = desc->jmax + 1;
@@ -1059,6 +1065,22 @@ int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *
     for (int i = 0; i < n_sets; ++i) {
         const int rc = (flags & JSS_ROLLOUT_AUTORESET) ? jss_step_autoreset(descs[i], states[i], actions[i], outs[i], stream)
                                                        : jss_step(descs[i], states[i], actions[i], outs[i], stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
+                          const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream) {
+    if (!descs || !states || !outs || !lgs) return JSS_E_NULL;
+    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
+    for (int i = 0; i < n_sets; ++i) {               // every set checked first: an argument error steps no set (as the HIP library)
+        int rc = check_args(descs[i], states[i], outs[i], true);
+        if (!rc) rc = check_logits(descs[i], lgs[i]);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        const int rc = jss_step_logits(descs[i], states[i], lgs[i], seed, flags, outs[i], stream);
         if (rc) return rc;
     }
     return 0;

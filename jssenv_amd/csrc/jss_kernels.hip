@@ -402,7 +402,15 @@ struct MultiParams {
 #ifndef JSS_MULTI_STEP_MIN_BLOCKS
 #define JSS_MULTI_STEP_MIN_BLOCKS 5
 #endif
-constexpr int multi_min_blocks(int mode) { return mode == kStep ? JSS_MULTI_STEP_MIN_BLOCKS : mode == kRollout1 ? 7 : mode == kReset ? 6 : 8; }
+// kLogits (jss_multi_step_logits): 5, like the grid's kStep -- 73 VGPRs, 6 wavefronts per SIMD as kStep's 74, no scratch
+// (6 compiles to 74 VGPRs with more SGPRs parked in VGPR lanes; the default 8 would cap it at 64 VGPRs and spill)
+#ifndef JSS_MULTI_LOGITS_MIN_BLOCKS
+#define JSS_MULTI_LOGITS_MIN_BLOCKS 5
+#endif
+constexpr int multi_min_blocks(int mode) {
+    return mode == kStep ? JSS_MULTI_STEP_MIN_BLOCKS : mode == kRollout1 ? 7 : mode == kReset ? 6
+         : mode == kLogits ? JSS_MULTI_LOGITS_MIN_BLOCKS : 8;
+}
 
 template <int MODE>
 __global__ __launch_bounds__(kBlock, multi_min_blocks(MODE)) void jss_multi_kernel(MultiParams mp) {
@@ -547,6 +555,16 @@ int launch_multi(Params *ps, int n, int n_steps, int n_sub, void *const *streams
     return rc ? rc : jrc;
 }
 
+// jss_step_logits' checks of a JssLogits against its set's description
+int check_logits(const JssDesc *d, const JssLogits *lg) {
+    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
+    if (lg->row != 0 && lg->row < (int64_t)d->jmax + 1) return JSS_E_SHAPE;
+    if (lg->row > (1 << 24)) return JSS_E_SHAPE;                         // (lane offsets are 32-bit)
+    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
+    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    return 0;
+}
+
 int check_multi(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs, bool need_out) {
     if (!descs || !states || (need_out && !outs)) return JSS_E_NULL;
     if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
@@ -628,11 +646,7 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
                     const JssOut *out, void *stream) {
     int rc = check_args(desc, state, out, true);
     if (rc) return rc;
-    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
-    if (lg->row != 0 && lg->row < (int64_t)desc->jmax + 1) return JSS_E_SHAPE;
-    if (lg->row > (1 << 24)) return JSS_E_SHAPE;                         // (lane offsets are 32-bit)
-    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
-    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
+    if ((rc = check_logits(desc, lg))) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.lg = *lg; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
     if (p.lg.row == 0) p.lg.row = desc->jmax + 1;
@@ -890,6 +904,24 @@ int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *
         ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
     }
     return launch_multi<kStep>(ps, n_sets, 1, 1, &stream, false);
+}
+
+// jss_step_logits over several sets: the fused grid's kLogits bodies (class-aware, as jss_multi_step), or one plain kLogits
+// launch per set when the combination has no body in the grid
+int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
+                          const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream) {
+    if (!lgs) return JSS_E_NULL;
+    int rc = check_multi(n_sets, descs, states, outs, true);
+    if (rc) return rc;
+    Params ps[16];
+    for (int i = 0; i < n_sets; ++i) {
+        if ((rc = check_logits(descs[i], lgs[i]))) return rc;
+        ps[i] = {};
+        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].lg = *lgs[i]; ps[i].seed = seed;
+        ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
+        if (ps[i].lg.row == 0) ps[i].lg.row = descs[i]->jmax + 1;
+    }
+    return launch_multi<kLogits>(ps, n_sets, 1, 1, &stream, false);
 }
 
 int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, int kind, uint64_t seed,

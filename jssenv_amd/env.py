@@ -459,8 +459,9 @@ class BatchedJssEnv:
         """step() with the action drawn on the device from the caller's logits (``jss_step_logits``): per env a masked
         categorical draw from softmax(logits / temperature) over the legal actions (jobs whose mask bit is set, NOPE at index
         J(env) when it is legal; Gumbel-max, keyed like the random policy by (seed, env id, episode, step)), its
-        log-probability and the entropy of the masked distribution, and the step itself -- one launch, the env state ends
-        bit-identical to ``step(info["action"])``.  ``temperature=0``: greedy (argmax, lowest index on ties; logp / entropy
+        log-probability and the entropy of the masked distribution, and the step itself -- one launch (a batch dealt out by
+        shape class: one grid over its class ranges, ``jss_multi_step_logits``), the env state ends bit-identical to
+        ``step(info["action"])``.  ``temperature=0``: greedy (argmax, lowest index on ties; logp / entropy
         for T = 1).  ``logits``: (B, >= jmax + 1) float32 or bfloat16 on the env's device, last dim contiguous; entries behind
         J(env) are never read as actions.  ``seed=None``: ``self.seed``.  ``autoreset=True``: an env that reported done is
         reset instead (action -2, logp 0, entropy 0); an env with no legal action is left alone (action -1, logp 0).
@@ -475,24 +476,37 @@ class BatchedJssEnv:
         self._refs()                                  # (refuses while a session is open)
         sd, flags = self.seed if seed is None else int(seed), _abi.ROLLOUT_AUTORESET if autoreset else 0
         with be.on_device():
-            ptr, row, dtype, keep = self._logits_arg(logits)
-        item = 2 if dtype == _abi.LOGITS_BF16 else 4
-        outs = (self._lg_action, self._lg_logp if logp else None, self._lg_entropy if entropy else None)
-        lgs = []
+            arg = self._logits_arg(logits)
+            if self._classes is not None:             # order='by_shape': one grid over the shape classes
+                lgs = [self._logits_struct(arg, temperature, logp, entropy, a) for a, _, _ in self._classes["spans"]]
+                ptrs = (C.POINTER(_abi.JssLogits) * len(lgs))(*[C.pointer(x) for x in lgs])
+                cs = self._classes["sets"]
+                rc = be.lib.jss_multi_step_logits(self._classes["n"], cs[0], cs[1], ptrs, sd, flags, cs[2], be.stream())
+                _abi.check(be.lib, rc, "jss_multi_step_logits")
+            else:
+                lg = self._logits_struct(arg, temperature, logp, entropy)
+                d, s, o = self._refs()
+                _abi.check(be.lib, be.lib.jss_step_logits(d, s, C.byref(lg), sd, flags, o, be.stream()), "jss_step_logits")
+        self._logits_keep = arg[3]                    # alive until the launch has read it
+        return self._obs(), self.reward, self.done, False, self._logits_info(logp, entropy)
 
-        def call(d, s, o, first, stream):             # (by shape class: one launch per range, every pointer at its first env)
-            at = lambda t, size: be.ptr(t) + first * size if t is not None else None      # noqa: E731
-            lgs.append(_abi.JssLogits(ptr + first * row * item, row, dtype, float(temperature),
-                                      at(outs[0], 4), at(outs[1], 4), at(outs[2], 4)))
-            return be.lib.jss_step_logits(d, s, C.byref(lgs[-1]), sd, flags, o, stream)
-        self._over_ranges(call, "jss_step_logits")
-        self._logits_keep = keep                      # alive until the launch has read it
+    def _logits_struct(self, arg, temperature, logp, entropy, first=0):
+        """JssLogits for the envs from `first` on: the logits (`_logits_arg`'s tuple) and the env's action / logp / entropy
+        buffers, every pointer at env `first`'s row"""
+        be = self.backend
+        ptr, row, dtype, _ = arg
+        item = 2 if dtype == _abi.LOGITS_BF16 else 4
+        at = lambda t, on: be.ptr(t) + first * 4 if on else None      # noqa: E731
+        return _abi.JssLogits(ptr + first * row * item, row, dtype, float(temperature), at(self._lg_action, True),
+                              at(self._lg_logp, logp), at(self._lg_entropy, entropy))
+
+    def _logits_info(self, logp, entropy):
         info = {"action": self._lg_action}
         if logp:
             info["logp"] = self._lg_logp
         if entropy:
             info["entropy"] = self._lg_entropy
-        return self._obs(), self.reward, self.done, False, info
+        return info
 
     def rollout(self, kind: Union[str, int] = "random", n_iter: int = 1, seed: Optional[int] = None,
                 autoreset: bool = True, explore: float = 0.0):
