@@ -44,6 +44,8 @@
  *   jss_step_logits <- the step of an on-policy learner: `a ~ softmax(logits masked by action_mask)` (the caller's policy
  *                   network's output), log pi(a) and the entropy, then JssEnv.step(a) -- the masked categorical draw fused
  *                   into the step launch
+ *   jss_generate <- JssEnv.__init__'s instance (jss_env.py:72-95) drawn on the device: a fresh Taillard (1993) J x M
+ *                   instance per env and episode, written into the env's own op / work / instance tables
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer in JssDesc/JssState/JssOut is a
@@ -84,7 +86,7 @@
 extern "C" {
 #endif
 
-#define JSS_ABI_VERSION 12
+#define JSS_ABI_VERSION 13
 
 #define JSS_MAX_JOBS 128
 #define JSS_MAX_MACHINES 64
@@ -534,6 +536,54 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
  * (a row outside [jmax + 1, 2^24] of ITS set: JSS_E_SHAPE; a bad dtype or temperature: JSS_E_KIND). */
 int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
                           const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream);
+
+/* ---- instances generated on the device (ABI v13) ----------------------------------------------------------------
+ * jss_generate writes a Taillard (1993) J x M instance into the tables of every env i with which == NULL or which[i] != 0,
+ * or with actions != NULL and actions[i] == JSS_ACTION_RESET (gen->actions; which == NULL and gen->actions != NULL: the
+ * actions alone decide): ops[i], rem[i] and inst[i] exactly as the host's pack_batch lays them out (machine << 16 |
+ * duration; suffix sums of the durations; the JSS_I_* record with J, M, the normalisers, their correctly rounded float32
+ * reciprocals 1.0f / (float)v -- (float) rounds to nearest, sum_op may exceed 2^24 -- and zeros in words 9-11).  Padding
+ * rows J..jmax-1 and columns M..mmax-1 are written as zeros.  Nothing else is touched: not the state, not other envs' tables.
+ *
+ * The draws are those of jssenv_amd.instances.taillard_instance / synthetic_arrays, bit for bit.  Two Lehmer streams per
+ * env (x <- 16807 x mod (2^31 - 1), the draw uses the new x), each draw
+ *       unif(low, high) = low + trunc(fl(fl(x / 2147483647.0) * (high - low + 1)))
+ * in IEEE double (a correctly rounded division, no contraction).  The time stream gives the durations, job-major:
+ * duration[j][k] = unif(dur_low, dur_high), draw j * M + k.  The machine stream gives each job's machine order: row = 0..M-1,
+ * then for k = 0..M-1: s = unif(k, M - 1) (draw j * M + k), swap row[k], row[s].
+ *
+ * Seeds.  Explicit (gen->time_seed and gen->machine_seed both non-NULL): x0 = time_seed[i] / machine_seed[i], e.g.
+ * ta01 = (840612802, 398197754).  A seed outside [1, 2^31 - 2] leaves env i's tables untouched (the stream would be
+ * degenerate; the host checks seeds before the call).  Derived (both NULL): with env_id = desc->env_ids[i] (or
+ * desc->env_id_base + i) and episode = state->env[i][JSS_H_EPISODE] + 1 (uint32) -- the number the env's next reset gives it:
+ *       time_seed    = 1 + rng_u32(gen->seed ^ JSS_GEN_SEED_XOR, env_id, episode, 0) % 2147483646
+ *       machine_seed = 1 + rng_u32(gen->seed ^ JSS_GEN_SEED_XOR, env_id, episode, 1) % 2147483646
+ * (rng_u32: the random policy's counter RNG, see jss_step_logits), so a batch sharded over ranks by env_id_base generates
+ * what one batch would, and an env's n-th episode always plays the same instance.
+ *
+ * Ordering.  jss_generate only writes tables.  An env whose tables were regenerated must be reset before it is stepped
+ * again -- jss_reset(which), JSS_ACTION_RESET, or the autoreset of jss_step_autoreset / jss_step_logits -- which copies J, M
+ * and the normalisers into env_const and caches the job's next ops: passing which = out->done (and the step's actions as
+ * gen->actions) right before an autoreset step on the same stream regenerates exactly the envs the step restarts.
+ *
+ * Requirements: desc->n_tables == desc->batch and desc->table_of_env == NULL (table i belongs to env i: no two envs share
+ * a table), 1 <= jmax <= JSS_MAX_JOBS, 1 <= mmax <= JSS_MAX_MACHINES, 1 <= jobs <= jmax, 1 <= machines <= mmax,
+ * 1 <= dur_low <= dur_high <= 65535; JSS_E_SHAPE otherwise.  JSS_E_NULL: desc, gen, gen->ops / rem / inst NULL, only one of
+ * the two seed arrays given, or derived seeds without state / state->env.  desc->ops / rem / inst / kernel / record_ints
+ * are not read. */
+#define JSS_GEN_SEED_XOR 0xD1B54A32D192ED03ULL   /* K_GEN: keys the derived instance seeds apart from every other draw */
+typedef struct JssGen {
+    int32_t *ops;                 /* [B][jmax][mmax] written: the arrays desc->ops / rem / inst describe, writable */
+    int32_t *rem;                 /* [B][jmax][mmax] written */
+    int32_t *inst;                /* [B][JSS_NI] written     */
+    const int64_t *time_seed;     /* [B] explicit seeds, or NULL (both NULL: derived seeds) */
+    const int64_t *machine_seed;  /* [B] */
+    const int32_t *actions;       /* [B] or NULL: envs with actions[i] == JSS_ACTION_RESET are generated as well */
+    uint64_t seed;                /* key of the derived seeds */
+    int32_t jobs, machines;       /* J, M of every generated instance */
+    int32_t dur_low, dur_high;    /* durations U{dur_low .. dur_high}; Taillard: 1, 99 */
+} JssGen;
+int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *stream);
 
 #ifdef JSS_PROFILING
 /* Instrumented builds only (tools/build_instrumented.py compiles with -DJSS_PROFILING; the shipped library does

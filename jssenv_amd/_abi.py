@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 STATE_LAYOUT = 7     # version of the state tensors' layout (checkpoints): unchanged since ABI v7
 MAX_JOBS, MAX_MACHINES = 128, 64
 F_TODO, F_CUR, F_LEFT, F_PERF, F_IDLE, F_IDLE_LAST, F_F4, F_NEXT, NF = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -35,6 +35,10 @@ ROLLOUT_AUTORESET, ROLLOUT_FORK_JOIN = 1, 2
 # jss_step_logits (JssLogits.dtype; K_LOGITS keys its Gumbel noise: rng_u32(seed ^ LOGITS_SEED_XOR, ...))
 LOGITS_F32, LOGITS_BF16 = 0, 1
 LOGITS_SEED_XOR = 0x2545F4914F6CDD1D
+# jss_generate (JssGen): derived instance seeds are 1 + rng_u32(seed ^ GEN_SEED_XOR, env_id, episode, 0 | 1) % GEN_SEED_MOD
+GEN_SEED_XOR = 0xD1B54A32D192ED03
+LCG_M = 2147483647                   # the Taillard streams' modulus; seeds lie in [1, LCG_M - 1]
+GEN_SEED_MOD = LCG_M - 1
 
 
 def cr_kind(due_date_factor: float = 1.5):
@@ -66,7 +70,7 @@ SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "j
            "jss_rollout", "jss_rollout_steps", "jss_rollout_steps_multi", "jss_trajectory", "jss_sync_check",
            "jss_step_autoreset", "jss_policy_step_steps", "jss_steps", "jss_session_open", "jss_session_post", "jss_session_wait", "jss_session_step", "jss_session_close",
            "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits",
-           "jss_multi_step_logits")
+           "jss_multi_step_logits", "jss_generate")
 
 _p = C.c_void_p
 
@@ -100,6 +104,12 @@ class JssSession(C.Structure):
 class JssLogits(C.Structure):
     _fields_ = [("logits", _p), ("row", C.c_int64), ("dtype", C.c_int32), ("temperature", C.c_float),
                 ("action", _p), ("logp", _p), ("entropy", _p)]
+
+
+class JssGen(C.Structure):
+    _fields_ = [("ops", _p), ("rem", _p), ("inst", _p), ("time_seed", _p), ("machine_seed", _p), ("actions", _p),
+                ("seed", C.c_uint64), ("jobs", C.c_int32), ("machines", C.c_int32), ("dur_low", C.c_int32),
+                ("dur_high", C.c_int32)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -156,6 +166,7 @@ def bind(lib):
     lib.jss_step_logits.argtypes = [D, S, C.POINTER(JssLogits), C.c_uint64, C.c_int32, O, _p]
     lib.jss_multi_step_logits.restype = C.c_int
     lib.jss_multi_step_logits.argtypes = [C.c_int32, PD, PS, C.POINTER(C.POINTER(JssLogits)), C.c_uint64, C.c_int32, PO, _p]
+    lib.jss_generate.restype, lib.jss_generate.argtypes = C.c_int, [D, S, C.POINTER(JssGen), _p, _p]
     if lib.jss_abi_version() != ABI_VERSION:
         raise RuntimeError(f"library ABI {lib.jss_abi_version()} != expected {ABI_VERSION}")
     return lib

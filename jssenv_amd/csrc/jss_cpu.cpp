@@ -803,6 +803,87 @@ int check_logits(const JssDesc *d, const JssLogits *lg) {
     return 0;
 }
 
+// jss_generate (include/jss_hip.h): a Taillard instance into env b's own tables, the draws of the two Lehmer streams walked
+// in order -- the same double arithmetic as the host generator and the kernel, the same float32 reciprocals
+constexpr int64_t kLcgM = 2147483647;
+constexpr uint64_t kGenSeedXor = JSS_GEN_SEED_XOR;
+
+int check_generate(const JssDesc *d, const JssState *s, const JssGen *g) {
+    if (!d || !g || !g->ops || !g->rem || !g->inst) return JSS_E_NULL;
+    if (!g->time_seed != !g->machine_seed) return JSS_E_NULL;
+    if (!g->time_seed && (!s || !s->env)) return JSS_E_NULL;
+    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 1 || d->mmax > JSS_MAX_MACHINES) return JSS_E_SHAPE;
+    if (d->n_tables != d->batch || d->table_of_env) return JSS_E_SHAPE;
+    if (g->jobs < 1 || g->jobs > d->jmax || g->machines < 1 || g->machines > d->mmax) return JSS_E_SHAPE;
+    if (g->dur_low < 1 || g->dur_low > g->dur_high || g->dur_high > 0xFFFF) return JSS_E_SHAPE;
+    return 0;
+}
+
+int lcg_unif(int64_t &x, int low, int n) {
+    x = x * 16807 % kLcgM;
+    return low + (int)((double)x / 2147483647.0 * (double)n);
+}
+
+int32_t rcp_bits(int v) {
+    const float r = 1.0f / (float)v;
+    int32_t bits;
+    std::memcpy(&bits, &r, 4);
+    return bits;
+}
+
+void generate_env(const JssDesc &d, const JssState *s, const JssGen &g, int b) {
+    int64_t xt, xm;
+    if (g.time_seed) {
+        xt = g.time_seed[b];
+        xm = g.machine_seed[b];
+        if (xt < 1 || xt >= kLcgM || xm < 1 || xm >= kLcgM) return;            // documented: tables untouched
+    } else {
+        const uint64_t id = (uint64_t)(d.env_ids ? d.env_ids[b] : d.env_id_base + b);
+        const uint32_t episode = (uint32_t)s->env[(size_t)b * JSS_NH + JSS_H_EPISODE] + 1u;
+        xt = 1 + rng_u32(g.seed ^ kGenSeedXor, id, episode, 0) % (uint32_t)(kLcgM - 1);
+        xm = 1 + rng_u32(g.seed ^ kGenSeedXor, id, episode, 1) % (uint32_t)(kLcgM - 1);
+    }
+    const int J = g.jobs, M = g.machines, jm = d.jmax, mm = d.mmax;
+    int32_t *ops = g.ops + (size_t)b * jm * mm, *rem = g.rem + (size_t)b * jm * mm;
+    std::memset(ops, 0, sizeof(int32_t) * jm * mm);
+    std::memset(rem, 0, sizeof(int32_t) * jm * mm);
+    const int n = g.dur_high - g.dur_low + 1;
+    for (int j = 0; j < J; ++j)                                                 // durations, job-major
+        for (int k = 0; k < M; ++k) ops[j * mm + k] = lcg_unif(xt, g.dur_low, n);
+    int max_op = 0, max_job = 0, sum = 0;
+    int machine[JSS_MAX_MACHINES];
+    for (int j = 0; j < J; ++j) {
+        for (int k = 0; k < M; ++k) machine[k] = k;
+        for (int k = 0; k < M; ++k) {                                           // machine order: the swap loop
+            const int t = lcg_unif(xm, k, M - k);
+            const int a = machine[k];
+            machine[k] = machine[t];
+            machine[t] = a;
+        }
+        int left = 0;
+        for (int k = M - 1; k >= 0; --k) {
+            const int dur = ops[j * mm + k];
+            left += dur;
+            rem[j * mm + k] = left;
+            ops[j * mm + k] = machine[k] << 16 | dur;
+            if (dur > max_op) max_op = dur;
+        }
+        if (left > max_job) max_job = left;
+        sum += left;
+    }
+    int32_t *rec = g.inst + (size_t)b * JSS_NI;
+    std::memset(rec, 0, sizeof(int32_t) * JSS_NI);
+    rec[JSS_I_JOBS] = J;
+    rec[JSS_I_MACHINES] = M;
+    rec[JSS_I_MAX_TIME_OP] = max_op;
+    rec[JSS_I_MAX_TIME_JOBS] = max_job;
+    rec[JSS_I_SUM_OP] = sum;
+    rec[JSS_I_RCP_MAX_TIME_OP] = rcp_bits(max_op);
+    rec[JSS_I_RCP_MAX_TIME_JOBS] = rcp_bits(max_job);
+    rec[JSS_I_RCP_SUM_OP] = rcp_bits(sum);
+    rec[JSS_I_RCP_MACHINES] = rcp_bits(M);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1110,6 +1191,29 @@ int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssStat
             rc = jss_rollout(descs[i], states[i], outs[i], kind, seed, explore_q16, n_steps, flags & JSS_ROLLOUT_AUTORESET, stream);
         if (rc) return rc;
     }
+    return 0;
+}
+
+int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *) {
+    const int rc = check_generate(desc, state, gen);
+    if (rc) return rc;
+    const JssDesc d = *desc;
+    const JssGen g = *gen;
+    const bool all = !which && !g.actions;
+    auto one = [&](int b) {
+        if (all || (which && which[b]) || (g.actions && g.actions[b] == JSS_ACTION_RESET)) generate_env(d, state, g, b);
+    };
+#ifdef _OPENMP
+    if (d.threads > 0) {
+#pragma omp parallel for schedule(static) num_threads(d.threads)
+        for (int b = 0; b < d.batch; ++b) one(b);
+    } else {
+#pragma omp parallel for schedule(static)
+        for (int b = 0; b < d.batch; ++b) one(b);
+    }
+#else
+    for (int b = 0; b < d.batch; ++b) one(b);
+#endif
     return 0;
 }
 

@@ -4,6 +4,7 @@
 //   jss_common.hpp      parameters, wave helpers, counter RNG
 //   jss_wave_env.hpp    one wavefront per env        (any J <= 128, M <= 64)
 //   jss_packed_env.hpp  64/G envs per wavefront      (J, M <= G, G = 16 or 32)
+//   jss_generate.hpp    Taillard instances drawn into the envs' own tables (jss_generate)
 //
 // No MFMA anywhere: the path is integer indexing, there is no dense contraction.
 #include <mutex>
@@ -12,6 +13,7 @@
 #include "jss_common.hpp"
 #include "jss_packed_env.hpp"
 #include "jss_wave_env.hpp"
+#include "jss_generate.hpp"
 
 namespace {
 using namespace jss;
@@ -575,6 +577,18 @@ int check_multi(int32_t n_sets, const JssDesc *const *descs, const JssState *con
     return 0;
 }
 
+// jss_generate's argument checks (include/jss_hip.h)
+int check_generate(const JssDesc *d, const JssState *s, const JssGen *g) {
+    if (!d || !g || !g->ops || !g->rem || !g->inst) return JSS_E_NULL;
+    if (!g->time_seed != !g->machine_seed) return JSS_E_NULL;                 // both seed arrays or neither
+    if (!g->time_seed && (!s || !s->env)) return JSS_E_NULL;                  // derived seeds read the episode
+    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 1 || d->mmax > JSS_MAX_MACHINES) return JSS_E_SHAPE;
+    if (d->n_tables != d->batch || d->table_of_env) return JSS_E_SHAPE;        // table i is env i's alone
+    if (g->jobs < 1 || g->jobs > d->jmax || g->machines < 1 || g->machines > d->mmax) return JSS_E_SHAPE;
+    if (g->dur_low < 1 || g->dur_low > g->dur_high || g->dur_high > 0xFFFF) return JSS_E_SHAPE;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -986,6 +1000,26 @@ int jss_rollout_steps_multi(int32_t n_sets, const JssDesc *const *descs, const J
         for (int i = 0; i < n_sets && !rc; ++i) rc = fire(ps[i], lps[i], streams[i]);
     const int jrc = fork_join ? join_streams(*ev, streams, n_sets) : 0;
     return rc ? rc : jrc;
+}
+
+// Taillard instances into the envs' own tables (jss_generate.hpp): sparse flags -> 64 envs' flags per wavefront, only the
+// flagged ones generated; no flags -> every env, kGenFullPerWave per wavefront
+int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *stream) {
+    const int rc = check_generate(desc, state, gen);
+    if (rc) return rc;
+    if (desc->batch == 0) return 0;
+    GenParams g = {};
+    g.ops = gen->ops; g.rem = gen->rem; g.inst = gen->inst;
+    g.time_seed = gen->time_seed; g.machine_seed = gen->machine_seed; g.actions = gen->actions; g.which = which;
+    g.env = gen->time_seed ? nullptr : state->env;
+    g.env_ids = desc->env_ids; g.env_id_base = desc->env_id_base; g.seed = gen->seed;
+    g.batch = desc->batch; g.jmax = desc->jmax; g.mmax = desc->mmax;
+    g.jobs = gen->jobs; g.machines = gen->machines; g.dur_low = gen->dur_low; g.dur_high = gen->dur_high;
+    g.per_wave = (which || gen->actions) ? kWave : kGenFullPerWave;
+    const long long waves = ((long long)desc->batch + g.per_wave - 1) / g.per_wave;
+    const int blocks = (int)((waves + kGenBlock / kWave - 1) / (kGenBlock / kWave));
+    hipLaunchKernelGGL(jss_generate_kernel, dim3(blocks), dim3(kGenBlock), 0, reinterpret_cast<hipStream_t>(stream), g);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

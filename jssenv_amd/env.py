@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _abi
 from .backends import _NULL_CTX, CpuBackend, HipBackend, _carve_numpy, make_backend  # noqa: F401  (re-exported: the historical home)
-from .instances import Instance, PackedBatch, pack_batch, resolve_instance
+from .instances import Instance, PackedBatch, MAX_DURATION, OP_MACHINE_SHIFT, pack_batch, resolve_instance
 
 
 class BatchedJssEnv:
@@ -49,7 +49,7 @@ class BatchedJssEnv:
     def __init__(self, instances, batch: Optional[int] = None, device=None, env_id_base: int = 0,
                  table_of_env: Optional[Sequence[int]] = None, seed: int = 0, kernel: Optional[str] = None,
                  compact: Optional[bool] = None, host_arena: bool = False, records: Optional[str] = None,
-                 order: Optional[str] = None, _backend=None):
+                 order: Optional[str] = None, _backend=None, _generated=None):
         self._owns_backend = _backend is None
         self.backend = be = _backend if _backend is not None else make_backend(device)
         if isinstance(instances, PackedBatch):
@@ -132,11 +132,19 @@ class BatchedJssEnv:
         self.record_ints = _abi.NFC if self.compact else _abi.NFM if self.medium else _abi.NF
         self.no_clocks = self.compact or self.medium           # time_until_available_machine is derived, not stored
 
+        # generated batches (BatchedJssEnv.generated): the device writes the tables (jss_generate), the host mirror `packed`
+        # is refreshed from them when it is read
+        self._gen, self._gen_struct, self._packed_stale = _generated, None, False
+        self.fresh = bool(_generated["fresh"]) if _generated else False
         with be.on_device():
             # instance tables
-            self._ops = be.from_numpy(pk.ops)
-            self._rem = be.from_numpy(pk.rem)
-            self._inst = be.from_numpy(pk.inst)
+            if _generated:
+                self._ops, self._rem = be.zeros(pk.ops.shape, "int32"), be.zeros(pk.ops.shape, "int32")
+                self._inst = be.zeros(pk.inst.shape, "int32")
+            else:
+                self._ops = be.from_numpy(pk.ops)
+                self._rem = be.from_numpy(pk.rem)
+                self._inst = be.from_numpy(pk.inst)
             self._table_of_env = None if table_of_env is None else be.from_numpy(self.table_of_env_host)
             self._env_ids = None
             # state (include/jss_hip.h JssState), outputs (JssOut) and the per-call scratch outputs: ONE allocation,
@@ -189,6 +197,125 @@ class BatchedJssEnv:
         self._classes = None
         if self._class_of_table is not None:
             self._build_class_views()
+        if _generated:
+            self._gen_struct = _abi.JssGen(p(self._ops), p(self._rem), p(self._inst), None, None, None, 0, _generated["jobs"],
+                                           _generated["machines"], *_generated["durations"])
+            self.generate()                    # (derived seeds: the instance the first reset starts)
+
+    @classmethod
+    def generated(cls, jobs: int, machines: int, batch: int, device=None, durations=(1, 99), instance_seed: int = 0,
+                  fresh: bool = True, **kw):
+        """A batch of ``batch`` envs on random Taillard ``jobs`` x ``machines`` instances drawn on the device
+        (``jss_generate``), one per env in its own table: durations U{durations[0] .. durations[1]} (Taillard: 1..99), seeds
+        derived from (``instance_seed``, global env id, episode) -- include/jss_hip.h states the draw.  Nothing is generated
+        on the host.  Record layout and kernel are what an equivalent ``synthetic_packed`` batch gets.
+
+        ``fresh=True``: every reset this object issues -- ``reset()``, ``reset(which)``, the autoreset of ``step`` /
+        ``step_logits`` / ``rollout(n_iter=1)``, explicit ``-2`` actions of ``step`` -- first regenerates the envs it restarts,
+        on the same stream, so every episode plays a new instance; the calls that restart envs inside one multi-step launch
+        refuse.  ``fresh=False``: the instances stay until ``generate()`` is called.  ``kw``: the constructor's (``seed``,
+        ``env_id_base``, ``kernel``, ``records``, ...)."""
+        jobs, machines, batch = int(jobs), int(machines), int(batch)
+        low, high = (int(v) for v in durations)
+        if not (1 <= jobs <= _abi.MAX_JOBS and 2 <= machines <= _abi.MAX_MACHINES):
+            raise ValueError(f"jobs must be in [1, {_abi.MAX_JOBS}] and machines in [2, {_abi.MAX_MACHINES}]")
+        if not 1 <= low <= high <= MAX_DURATION:
+            raise ValueError("durations must satisfy 1 <= low <= high <= 65535")
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        if kw.get("table_of_env") is not None or kw.get("order") == "by_shape":
+            raise ValueError("a generated batch has one table per env")
+        z = np.zeros((), dtype=np.int32)
+        full = lambda v: np.full(batch, v, dtype=np.int32)      # noqa: E731
+        # the shape of the batch only: the tables are allocated on the device and written there
+        pk = PackedBatch(ops=np.broadcast_to(z, (batch, jobs, machines)), rem=np.broadcast_to(z, (batch, jobs, machines)),
+                         inst=np.broadcast_to(z, (batch, _abi.NI)), jobs=full(jobs), machines=full(machines),
+                         max_time_op=full(0), max_time_jobs=full(0), sum_op=full(0), jmax=jobs, mmax=machines)
+        gen = {"jobs": jobs, "machines": machines, "durations": (low, high), "fresh": bool(fresh), "seed": int(instance_seed)}
+        return cls(pk, batch=batch, device=device, _generated=gen, **kw)
+
+    @property
+    def instance_seed(self):
+        """Key of the derived instance seeds of a generated batch (``generated(instance_seed=...)``)."""
+        return self._gen["seed"] if self._gen else None
+
+    @instance_seed.setter
+    def instance_seed(self, value):
+        if not self._gen:
+            raise ValueError("only a generated batch has an instance seed")
+        self._gen["seed"] = int(value)
+
+    @property
+    def packed(self) -> PackedBatch:
+        """Host mirror of the instance tables (PackedBatch).  A generated batch's tables are written by the device: the
+        mirror is fetched from there (one synchronising copy) the first time it is read after a ``generate``."""
+        if self.__dict__.get("_packed_stale"):
+            self._refresh_packed()
+        return self.__dict__["_packed"]
+
+    @packed.setter
+    def packed(self, pk):
+        self.__dict__["_packed"] = pk
+
+    def _refresh_packed(self):
+        be = self.backend
+        with be.on_device():
+            ops, rem, inst = (np.ascontiguousarray(be.numpy(t)) for t in (self._ops, self._rem, self._inst))
+        as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)      # noqa: E731
+        self.__dict__["_packed"] = PackedBatch(ops=ops, rem=rem, inst=inst, jobs=as32(inst[:, _abi.I_JOBS]),
+                                               machines=as32(inst[:, _abi.I_MACHINES]), max_time_op=as32(inst[:, _abi.I_MAX_TIME_OP]),
+                                               max_time_jobs=as32(inst[:, _abi.I_MAX_TIME_JOBS]), sum_op=as32(inst[:, _abi.I_SUM_OP]),
+                                               jmax=self.jmax, mmax=self.mmax)
+        self._packed_stale = False
+
+    def instance(self, i: int) -> Instance:
+        """The Instance env ``i`` currently plays (its table as it is now: for a generated batch, read from the device)."""
+        i = int(i)
+        if not 0 <= i < self.batch:
+            raise IndexError("env index out of range")
+        J, M = int(self.jobs_per_env[i]), int(self.machines_per_env[i])
+        ops = self.packed.ops[int(self.table_of_env_host[i])][:J, :M]
+        return Instance(f"env{i}", ops >> OP_MACHINE_SHIFT, ops & MAX_DURATION)
+
+    def generate(self, which=None, seed: Optional[int] = None, time_seed=None, machine_seed=None, _actions=None):
+        """Draw new Taillard instances into the tables of the envs with ``which[i] != 0`` (None: every env) on the device
+        (``jss_generate``; ``which`` a device tensor such as ``self.done``, or a host mask).  Seeds: explicit
+        ``time_seed`` / ``machine_seed`` (host arrays of B integers in [1, 2^31 - 2]: e.g. ta01 = 840612802, 398197754), or
+        derived from (``seed``, default ``instance_seed``; the env's global id; the episode its next reset starts).  The
+        envs must be reset before they are stepped again (``reset(which)``, a ``-2`` action, an autoreset).  Generated
+        batches only."""
+        if not self._gen:
+            raise ValueError("generate() needs a batch made by BatchedJssEnv.generated()")
+        be, B = self.backend, self.batch
+        d, s, _ = self._refs()
+        g = self._gen_struct
+        if (time_seed is None) != (machine_seed is None):
+            raise ValueError("give both time_seed and machine_seed, or neither")
+        seeds = []
+        if time_seed is not None:
+            for x in (time_seed, machine_seed):
+                a = np.asarray(be.numpy(x) if hasattr(x, "data_ptr") else x)
+                if a.shape != (B,) or a.dtype.kind not in "iu":
+                    raise ValueError(f"explicit seeds must be {B} integers")
+                if a.min() < 1 or a.max() > _abi.LCG_M - 1:
+                    raise ValueError("seeds must be in [1, 2^31 - 2]")
+                seeds.append(np.ascontiguousarray(a, dtype=np.int64))
+        with be.on_device():
+            keep = [be.from_numpy(a) for a in seeds]
+            w = self._mask_arg(which)
+            g.time_seed, g.machine_seed = (be.ptr(keep[0]), be.ptr(keep[1])) if keep else (None, None)
+            g.actions = None if _actions is None else be.ptr(_actions)
+            g.seed = (self._gen["seed"] if seed is None else int(seed)) & ((1 << 64) - 1)
+            rc = be.lib.jss_generate(d, s, C.byref(g), be.ptr(w), be.stream())
+            g.time_seed = g.machine_seed = g.actions = None
+        _abi.check(be.lib, rc, "jss_generate")
+        self._gen_keep = keep                      # alive until the launch has read them
+        self._packed_stale = True
+
+    def _refuse_fresh(self, what):
+        if self.fresh:
+            raise RuntimeError(f"{what} restarts envs inside one launch, where no fresh instance can be generated for them: "
+                               "not available with fresh=True (use step / step_logits, or fresh=False)")
 
     @property
     def steps_by_shape_class(self) -> bool:
@@ -332,6 +459,8 @@ class BatchedJssEnv:
         """reset() of jss_env.py:145-181 for every env (or those with which[i] != 0). Returns the obs dict."""
         be = self.backend
         d, s, o = self._refs()
+        if self.fresh:                           # a new instance for every env this reset restarts
+            self.generate(which)
         with be.on_device():
             w = self._mask_arg(which)
             if self._classes is not None:        # order='by_shape': one grid over the shape classes
@@ -355,6 +484,8 @@ class BatchedJssEnv:
         d, s, o = self._refs()
         with be.on_device():
             a = self._stage(self._act_in, actions, "int32")   # the caller's int32 tensor itself, or a copy into our buffer
+            if self.fresh:                # new instances for the envs this step restarts: -2 actions, and the done ones
+                self.generate(self.done if autoreset else None, _actions=a)
             # autoreset: envs that reported done last time are reset instead of stepped, in the same launch (the kernel
             # looks at the done flags itself: jss_step_autoreset)
             if self._classes is not None:
@@ -477,6 +608,8 @@ class BatchedJssEnv:
         sd, flags = self.seed if seed is None else int(seed), _abi.ROLLOUT_AUTORESET if autoreset else 0
         with be.on_device():
             arg = self._logits_arg(logits)
+            if self.fresh and autoreset:  # new instances for the envs this step restarts (the done ones)
+                self.generate(self.done)
             if self._classes is not None:             # order='by_shape': one grid over the shape classes
                 lgs = [self._logits_struct(arg, temperature, logp, entropy, a) for a, _, _ in self._classes["spans"]]
                 ptrs = (C.POINTER(_abi.JssLogits) * len(lgs))(*[C.pointer(x) for x in lgs])
@@ -517,6 +650,10 @@ class BatchedJssEnv:
         k = _abi.policy_code(kind)
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         d, s, o = self._refs()
+        if autoreset and self.fresh:
+            if int(n_iter) > 1:
+                self._refuse_fresh("rollout(n_iter > 1, autoreset=True)")
+            self.generate(self.done)      # one iteration: it restarts exactly the envs found done
         with be.on_device():
             if self._classes is not None and int(n_iter) == 1:
                 streams = (C.c_void_p * 1)(be.stream())
@@ -537,6 +674,8 @@ class BatchedJssEnv:
         another's.  Results are identical to ``steps`` calls of ``rollout(n_iter=1)``; outputs hold the last step."""
         if not self._is_reset:
             raise RuntimeError("call reset() before rollout_steps()")
+        if autoreset:
+            self._refuse_fresh("rollout_steps(autoreset=True)")
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
@@ -569,6 +708,8 @@ class BatchedJssEnv:
         Python loop ``for _ in range(steps): env.step(env.policy(kind), autoreset=autoreset)``."""
         if not self._is_reset:
             raise RuntimeError("call reset() before policy_step_steps()")
+        if autoreset:
+            self._refuse_fresh("policy_step_steps(autoreset=True)")
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
@@ -597,6 +738,8 @@ class BatchedJssEnv:
         touches the results (include/jss_hip.h: "the caller orders streams[] against its own stream")."""
         if not self._is_reset:
             raise RuntimeError("call reset() before rollout_steps()")
+        if autoreset:
+            self._refuse_fresh("rollout_steps(autoreset=True)")
         be = self.backend
         if not hasattr(be, "stream_array"):
             return lambda: self.rollout_steps(kind, steps, n_sub, seed, autoreset, explore)
@@ -641,6 +784,8 @@ class BatchedJssEnv:
         tensors are allocated here (outside the hot loop: allocate once, pass them back in)."""
         if not self._is_reset:
             raise RuntimeError("call reset() before trajectory()")
+        if autoreset:
+            self._refuse_fresh("trajectory(autoreset=True)")
         be = self.backend
         K, B, J = int(steps), self.batch, self.jmax
         shapes = {"real_obs": ((K, B, J, 7), "float32"), "action_mask": ((K, B, J + 1), "uint8"),
@@ -722,6 +867,8 @@ class BatchedJssEnv:
         out = {}
         with be.on_device():
             a = be.as_device(actions, "int32")
+            if self.fresh and bool((a == _abi.ACTION_RESET).any()):     # (a host synchronisation: fresh batches only)
+                self._refuse_fresh("steps() with -2 actions")
             for name in record:
                 shp, dtype = shapes[name]
                 t = None if buffers is None else buffers.get(name)
@@ -926,6 +1073,10 @@ class BatchedJssEnv:
                      "ops": self.packed.ops.copy(),
                      # the global env ids key the per-env RNG streams: a resumed run continues them only on the same ids
                      "env_ids": (np.zeros(0, dtype=np.int64) if self._env_ids is None else n(self._env_ids).astype(np.int64))}
+        if self._gen:                              # a generated batch: its tables are part of the state
+            pk = self.packed
+            d["meta"].update({"gen_rem": pk.rem.copy(), "gen_inst": pk.inst.copy(), "gen_seed": self._gen["seed"],
+                              "gen_durations": np.asarray(self._gen["durations"], dtype=np.int64)})
         return d
 
     def load_state_dict(self, d):
@@ -935,7 +1086,15 @@ class BatchedJssEnv:
             raise ValueError(f"checkpoint was written with state layout v{m.get('abi')}, this build is v{_abi.STATE_LAYOUT}")
         if int(m.get("record_ints", _abi.NF)) != self.record_ints:
             raise ValueError("checkpoint uses another job-record layout (compact / medium / full)")
-        if (int(m["batch"]), int(m["jmax"]), int(m["mmax"])) != (self.batch, self.jmax, self.mmax) or \
+        if bool(self._gen) != ("gen_inst" in m):
+            raise ValueError("checkpoint and batch differ in kind: one of them is a generated batch")
+        if self._gen:                              # the tables come with the checkpoint: the shapes and the draw must match
+            same = (np.asarray(m["ops"]).shape == (self.batch, self.jmax, self.mmax) and
+                    tuple(np.asarray(m["gen_durations"]).tolist()) == self._gen["durations"] and
+                    bool((np.asarray(m["gen_inst"])[:, :2] == (self._gen["jobs"], self._gen["machines"])).all()))
+            if not same:
+                raise ValueError("checkpoint belongs to a generated batch of another shape or duration range")
+        elif (int(m["batch"]), int(m["jmax"]), int(m["mmax"])) != (self.batch, self.jmax, self.mmax) or \
                 not np.array_equal(m["ops"], self.packed.ops) or not np.array_equal(m["table_of_env"], self.table_of_env_host):
             raise ValueError("checkpoint belongs to a different batch (shape or instances differ)")
         mine = np.zeros(0, dtype=np.int64) if self._env_ids is None else self.backend.numpy(self._env_ids).astype(np.int64)
@@ -946,6 +1105,11 @@ class BatchedJssEnv:
             self.backend.sync()
             for k in self._saved_tensors():
                 self.backend.copy_into(getattr(self, k), np.asarray(d[k]))
+            if self._gen:
+                for t, k in ((self._ops, "ops"), (self._rem, "gen_rem"), (self._inst, "gen_inst")):
+                    self.backend.copy_into(t, np.ascontiguousarray(m[k], dtype=np.int32))
+        if self._gen:
+            self._gen["seed"], self._packed_stale = int(m["gen_seed"]), True
         self.seed, self._is_reset = int(m["seed"]), True
 
     def save_checkpoint(self, path):

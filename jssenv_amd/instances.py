@@ -183,18 +183,29 @@ def _lcg_unif(x: np.ndarray, low, high) -> np.ndarray:
     return low + ((x / _LCG_M) * (high - low + 1)).astype(np.int64)
 
 
-def synthetic_arrays(n: int, jobs: int, machines: int, first: int = 0):
+def synthetic_arrays(n: int, jobs: int, machines: int, first: int = 0, durations=(1, 99), seeds=None):
     """The instances of ``synthetic_batch(n, jobs, machines, first)`` as two (n, J, M) int32 arrays
     (machine, duration), generated for all n instances at once (every instance has its own LCG streams, so the
-    J*M draws vectorise over the instance axis).  65 536 instances of 15x15 take about a second."""
-    idx = first + np.arange(n, dtype=np.int64)
-    xt, xm = 1 + 2 * idx, 2 + 2 * idx
-    if n and (xm.max() >= _LCG_M):
+    J*M draws vectorise over the instance axis).  65 536 instances of 15x15 take about a second.
+
+    ``durations``: the (low, high) of the duration draws (Taillard: 1, 99).  ``seeds``: (time_seeds, machine_seeds), two
+    length-n integer arrays in [1, 2^31 - 2] used instead of ``1 + 2i`` / ``2 + 2i`` (what ``jss_generate`` draws from)."""
+    if seeds is None:
+        idx = first + np.arange(n, dtype=np.int64)
+        xt, xm = 1 + 2 * idx, 2 + 2 * idx
+    else:
+        xt, xm = (np.array(a, dtype=np.int64).reshape(-1) for a in seeds)
+        if xt.shape != (n,) or xm.shape != (n,):
+            raise ValueError(f"seeds must be two arrays of length {n}")
+    if n and (min(xt.min(), xm.min()) < 1 or max(xt.max(), xm.max()) >= _LCG_M):
         raise ValueError("seed must be in [1, 2^31-2]")
+    low, high = (int(v) for v in durations)
+    if not 1 <= low <= high <= MAX_DURATION:
+        raise ValueError("durations must satisfy 1 <= low <= high <= 65535")
     duration = np.zeros((n, jobs, machines), dtype=np.int32)
     for j in range(jobs):
         for k in range(machines):
-            duration[:, j, k] = _lcg_unif(xt, 1, 99)
+            duration[:, j, k] = _lcg_unif(xt, low, high)
     machine = np.tile(np.arange(machines, dtype=np.int32), (n, jobs, 1))
     rows = np.arange(n)
     for j in range(jobs):
@@ -205,12 +216,19 @@ def synthetic_arrays(n: int, jobs: int, machines: int, first: int = 0):
     return machine, duration
 
 
-def synthetic_packed(n: int, jobs: int, machines: int, first: int = 0) -> "PackedBatch":
-    """``pack_batch(synthetic_batch(...))`` without building n Instance objects (bench-sized batches)."""
-    machine, duration = synthetic_arrays(n, jobs, machines, first)
-    ops = ((machine << OP_MACHINE_SHIFT) | duration).astype(np.int32)
+def synthetic_packed(n: int, jobs: int, machines: int, first: int = 0, durations=(1, 99), seeds=None) -> "PackedBatch":
+    """``pack_batch(synthetic_batch(...))`` without building n Instance objects (bench-sized batches).  ``durations`` /
+    ``seeds``: as ``synthetic_arrays``."""
+    machine, duration = synthetic_arrays(n, jobs, machines, first, durations, seeds)
+    return _pack_arrays(machine, duration)
+
+
+def _pack_arrays(machine, duration) -> "PackedBatch":
+    """PackedBatch of n instances of one shape given as (n, J, M) machine / duration arrays"""
+    n, jobs, machines = duration.shape
+    ops = ((machine.astype(np.int32) << OP_MACHINE_SHIFT) | duration).astype(np.int32)
     rem = np.cumsum(duration[:, :, ::-1], axis=2)[:, :, ::-1].astype(np.int32)
-    jl = duration.sum(axis=2)
+    jl = duration.astype(np.int64).sum(axis=2)
     mto, mtj, sop = duration.max(axis=(1, 2)), jl.max(axis=1), jl.sum(axis=1)
     rec = np.zeros((n, INST_RECORD_INTS), dtype=np.int32)
     rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4] = jobs, machines, mto, mtj, sop

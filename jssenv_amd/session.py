@@ -49,6 +49,8 @@ class StepSession:
             raise RuntimeError("call reset() before opening a session")
         if getattr(env, "_session", None) is not None:
             raise RuntimeError("this env already has an open session")
+        if getattr(env, "fresh", False):         # a JSS_ACTION_RESET inside the resident kernel restarts the env on its old table
+            env._refuse_fresh("a step session")
         self.env, self.depth = env, int(depth)
         be = self.be = env.backend
         B = env.batch

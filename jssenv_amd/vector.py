@@ -28,10 +28,10 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
     class's constructor -- whose signature differs between gymnasium 0.29 and 1.x -- is not called)"""
 
     def __init__(self, instances, num_envs: Optional[int] = None, device=None, to_numpy: bool = False, order: Optional[str] = None,
-                 _backend=None):
+                 _backend=None, _env=None):
         # order="by_shape": a list of instances of different shapes, the envs dealt onto them class by class and stepped by
         # class-specialised kernel bodies on the padded tensors (BatchedJssEnv); `step` stays ONE launch (jss_multi_step)
-        self.env = BatchedJssEnv(instances, batch=num_envs, device=device, order=order, _backend=_backend)
+        self.env = _env if _env is not None else BatchedJssEnv(instances, batch=num_envs, device=device, order=order, _backend=_backend)
         self.num_envs = self.env.batch
         self.to_numpy = to_numpy
         self.jobs_per_env = self.env.jobs_per_env
@@ -53,6 +53,16 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
             self.single_action_space = self.single_observation_space = None
             self.action_space = self.observation_space = None
         self.closed = False
+
+    @classmethod
+    def generated(cls, jobs: int, machines: int, num_envs: int, device=None, durations=(1, 99), instance_seed: int = 0,
+                  fresh: bool = True, to_numpy: bool = False, _backend=None, **kw):
+        """A vector env on random Taillard jobs x machines instances drawn on the device (BatchedJssEnv.generated): with
+        ``fresh=True`` every episode of every env -- the first one and each autoreset -- plays a new instance, generated in
+        the same stream as the step that restarts it."""
+        env = BatchedJssEnv.generated(jobs, machines, num_envs, device=device, durations=durations, instance_seed=instance_seed,
+                                      fresh=fresh, _backend=_backend, **kw)
+        return cls(None, to_numpy=to_numpy, _env=env)
 
     def _out(self, x):
         return self.env.backend.numpy(x) if self.to_numpy else x
