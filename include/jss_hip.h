@@ -46,6 +46,8 @@
  *                   into the step launch
  *   jss_generate <- JssEnv.__init__'s instance (jss_env.py:72-95) drawn on the device: a fresh Taillard (1993) J x M
  *                   instance per env and episode, written into the env's own op / work / instance tables
+ *   jss_clone    <- copy.deepcopy(env) of a reference env mid-episode (what MCTS / beam search / the pilot method do at
+ *                   every expansion), over batches: env k of one batch becomes a copy of env src_of_dst[k] of another
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer in JssDesc/JssState/JssOut is a
@@ -86,7 +88,7 @@
 extern "C" {
 #endif
 
-#define JSS_ABI_VERSION 13
+#define JSS_ABI_VERSION 14
 
 #define JSS_MAX_JOBS 128
 #define JSS_MAX_MACHINES 64
@@ -199,6 +201,7 @@ extern "C" {
 #define JSS_ERR_NOPE_IDLE 2      /* NOPE/advance with no busy machine (reference: IndexError, jss_env.py:517) */
 #define JSS_ERR_BAD_ACTION 4     /* action < -2 or > J: ignored (reference: IndexError) */
 #define JSS_ERR_BAD_LOGITS 8     /* jss_step_logits: a legal action's logit was NaN or +inf (read as -inf) */
+#define JSS_ERR_BAD_INDEX 16     /* jss_clone: src_of_dst[k] outside [-1, src batch): env k left as it was, this bit set */
 
 #define JSS_ACTION_SKIP (-1) /* batched step: this env is not stepped; its state, reward, done and makespan
                                 are left as they were (observation and mask are rewritten unchanged) */
@@ -584,6 +587,36 @@ typedef struct JssGen {
     int32_t dur_low, dur_high;    /* durations U{dur_low .. dur_high}; Taillard: 1, 99 */
 } JssGen;
 int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *stream);
+
+/* ---- clone env states (ABI v14) ---------------------------------------------------------------------------------
+ * jss_clone makes every destination env k a copy of source env src_of_dst[k] (a gather; src_of_dst[k] == -1 leaves env k
+ * untouched, so a large pool can be updated without compacting the index first).  "Env k becomes a copy of env i" means that
+ * every later call treats k exactly as it would treat i; only the env's identity and its accounting differ.
+ *   Copied, byte for byte, padding rows and columns included: the header (clock, episode, step, status with its error bits
+ *   and NOPE flag), env_const, the job records (whichever layout), the machine clocks (full records only), the solution,
+ *   the last outputs (real_obs, action_mask, reward, done, makespan) and the env's instance assignment: its table_of_env
+ *   entry (batches with table_of_env), or its own op / work / instance table rows (one table per env: n_tables == batch,
+ *   no table_of_env -- generated and synthetic per-env batches; env i's table becomes table k, and env_const's JSS_C_TABLE
+ *   word says k, as a reset of env k would write it).  A batch that shares one table has nothing to copy there.
+ *   Not copied: the counters (they count the work a slot did: not read, not written) and the global env id (JssDesc.env_ids
+ *   / env_id_base + k stays the destination's).  The RNG is keyed by (seed, global env id, episode, step), so two clones of
+ *   one parent draw different random actions, logits samples and fresh instances from then on -- what sampling-based search
+ *   needs.  A caller who wants a clone to replay its parent's draws gives it the parent's id (JssDesc.env_ids).
+ * The two batch sizes may differ (a fork: B_dst envs drawn from B_src).  Source and destination may be the same arrays only if
+ * no env is both read and written in the call (the library does not check this).  Stream-ordered on `stream`; allocates
+ * nothing and never synchronises (it can be captured into a graph).
+ * Errors (nothing is launched then): JSS_E_NULL for a NULL desc, state or out pointer (JssState.machine may be NULL where the
+ * step calls allow it: compact and medium records) or a NULL src_of_dst; JSS_E_SHAPE when the descs differ in jmax, mmax or
+ * record_ints, in the table kind (one shared table, table_of_env, one table per env -- a batch of ONE env on one table
+ * counts as either) or, for the two shared kinds, in n_tables, and when a dst_tables pointer the copy needs is NULL.  A
+ * src_of_dst[k] outside [-1, src batch) is no argument error: env k is left as it was and JSS_ERR_BAD_INDEX is set in its
+ * status byte. */
+typedef struct JssCloneDst {   /* the destination's assignment arrays, writable (as JssGen's ops / rem / inst) */
+    int32_t *table_of_env;     /* [B_dst] when dst_desc->table_of_env != NULL */
+    int32_t *ops, *rem, *inst; /* per-env tables: the arrays dst_desc->ops / rem / inst describe */
+} JssCloneDst;
+int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,
+              const JssDesc *src_desc, const JssState *src, const JssOut *src_out, const int32_t *src_of_dst, void *stream);
 
 #ifdef JSS_PROFILING
 /* Instrumented builds only (tools/build_instrumented.py compiles with -DJSS_PROFILING; the shipped library does

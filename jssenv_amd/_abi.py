@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 STATE_LAYOUT = 7     # version of the state tensors' layout (checkpoints): unchanged since ABI v7
 MAX_JOBS, MAX_MACHINES = 128, 64
 F_TODO, F_CUR, F_LEFT, F_PERF, F_IDLE, F_IDLE_LAST, F_F4, F_NEXT, NF = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -28,7 +28,7 @@ STATUS_NOOP = 256
 F4_ONE = -1
 I_JOBS, I_MACHINES, I_MAX_TIME_OP, I_MAX_TIME_JOBS, I_SUM_OP = 0, 1, 2, 3, 4
 I_RCP_MAX_TIME_OP, I_RCP_MAX_TIME_JOBS, I_RCP_SUM_OP, I_RCP_MACHINES, NI = 5, 6, 7, 8, 12
-ERR_ILLEGAL_ACTION, ERR_NOPE_IDLE, ERR_BAD_ACTION, ERR_BAD_LOGITS = 1, 2, 4, 8
+ERR_ILLEGAL_ACTION, ERR_NOPE_IDLE, ERR_BAD_ACTION, ERR_BAD_LOGITS, ERR_BAD_INDEX = 1, 2, 4, 8, 16
 ACTION_SKIP, ACTION_RESET, ACTION_CLOSE = -1, -2, -3
 POLICY = {"random": 0, "FIFO": 1, "SPT": 2, "MWR": 3, "LWR": 4, "MOR": 5, "LOR": 6, "CR": 7}
 ROLLOUT_AUTORESET, ROLLOUT_FORK_JOIN = 1, 2
@@ -70,7 +70,7 @@ SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "j
            "jss_rollout", "jss_rollout_steps", "jss_rollout_steps_multi", "jss_trajectory", "jss_sync_check",
            "jss_step_autoreset", "jss_policy_step_steps", "jss_steps", "jss_session_open", "jss_session_post", "jss_session_wait", "jss_session_step", "jss_session_close",
            "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits",
-           "jss_multi_step_logits", "jss_generate")
+           "jss_multi_step_logits", "jss_generate", "jss_clone")
 
 _p = C.c_void_p
 
@@ -110,6 +110,10 @@ class JssGen(C.Structure):
     _fields_ = [("ops", _p), ("rem", _p), ("inst", _p), ("time_seed", _p), ("machine_seed", _p), ("actions", _p),
                 ("seed", C.c_uint64), ("jobs", C.c_int32), ("machines", C.c_int32), ("dur_low", C.c_int32),
                 ("dur_high", C.c_int32)]
+
+
+class JssCloneDst(C.Structure):
+    _fields_ = [("table_of_env", _p), ("ops", _p), ("rem", _p), ("inst", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -167,6 +171,7 @@ def bind(lib):
     lib.jss_multi_step_logits.restype = C.c_int
     lib.jss_multi_step_logits.argtypes = [C.c_int32, PD, PS, C.POINTER(C.POINTER(JssLogits)), C.c_uint64, C.c_int32, PO, _p]
     lib.jss_generate.restype, lib.jss_generate.argtypes = C.c_int, [D, S, C.POINTER(JssGen), _p, _p]
+    lib.jss_clone.restype, lib.jss_clone.argtypes = C.c_int, [D, S, O, C.POINTER(JssCloneDst), D, S, O, _p, _p]
     if lib.jss_abi_version() != ABI_VERSION:
         raise RuntimeError(f"library ABI {lib.jss_abi_version()} != expected {ABI_VERSION}")
     return lib

@@ -803,6 +803,40 @@ int check_logits(const JssDesc *d, const JssLogits *lg) {
     return 0;
 }
 
+// jss_clone (include/jss_hip.h): env k <- env src_of_dst[k], row by row.  The table kind of a batch: 0 one shared table,
+// 1 table_of_env, 2 one table per env, 3 one env on one table (either of 0 and 2)
+int clone_table_kind(const JssDesc *d) {
+    if (d->table_of_env) return 1;
+    if (d->n_tables == 1) return d->batch == 1 ? 3 : 0;
+    return 2;
+}
+
+int clone_record_ints(const JssDesc *d) { return d->record_ints == JSS_NFC || d->record_ints == JSS_NFM ? d->record_ints : JSS_NF; }
+
+// *mode: 0 no instance assignment to copy, 1 the table_of_env entry, 2 the env's own table rows
+int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout, const JssCloneDst *dt, const JssDesc *sd,
+                const JssState *ss, const JssOut *sout, const int32_t *src_of_dst, int *mode) {
+    if (!src_of_dst) return JSS_E_NULL;
+    int rc = check_args(dd, ds, dout, true);
+    if (!rc) rc = check_args(sd, ss, sout, true);
+    if (rc) return rc;
+    if (dd->jmax != sd->jmax || dd->mmax != sd->mmax || clone_record_ints(dd) != clone_record_ints(sd)) return JSS_E_SHAPE;
+    const int a = clone_table_kind(dd), b = clone_table_kind(sd);
+    if (a == 1 || b == 1) {
+        if (a != b || dd->n_tables != sd->n_tables) return JSS_E_SHAPE;
+        *mode = 1;
+    } else if (a == 0 || b == 0) {
+        if (a == 2 || b == 2) return JSS_E_SHAPE;
+        *mode = 0;
+    } else {
+        *mode = 2;
+    }
+    if (*mode == 1 && (!dt || !dt->table_of_env)) return JSS_E_SHAPE;
+    if (*mode == 2 && (!dt || !dt->ops || !dt->rem || !dt->inst)) return JSS_E_SHAPE;
+    if (*mode == 2 && !sd->rem) return JSS_E_NULL;
+    return 0;
+}
+
 // jss_generate (include/jss_hip.h): a Taillard instance into env b's own tables, the draws of the two Lehmer streams walked
 // in order -- the same double arithmetic as the host generator and the kernel, the same float32 reciprocals
 constexpr int64_t kLcgM = 2147483647;
@@ -1213,6 +1247,55 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
     }
 #else
     for (int b = 0; b < d.batch; ++b) one(b);
+#endif
+    return 0;
+}
+
+int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,
+              const JssDesc *src_desc, const JssState *src, const JssOut *src_out, const int32_t *src_of_dst, void *) {
+    int mode = 0;
+    const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode);
+    if (rc) return rc;
+    const JssDesc dd = *dst_desc, sd = *src_desc;
+    const size_t J = dd.jmax, M = dd.mmax, R = clone_record_ints(&dd);
+    auto row = [](void *d, const void *s, size_t bytes, size_t k, size_t i) {
+        std::memcpy(static_cast<char *>(d) + k * bytes, static_cast<const char *>(s) + i * bytes, bytes);
+    };
+    auto one = [&](int k) {
+        const int i = src_of_dst[k];
+        if (i == -1) return;
+        if (i < -1 || i >= sd.batch) {
+            dst->env[(size_t)k * JSS_NH + JSS_H_STATUS] |= JSS_ERR_BAD_INDEX;
+            return;
+        }
+        row(dst->env, src->env, JSS_NH * 4, k, i);
+        row(dst->env_const, src->env_const, JSS_NC * 4, k, i);
+        row(dst->job, src->job, J * R * 4, k, i);
+        if (R == JSS_NF) row(dst->machine, src->machine, M * 4, k, i);
+        row(dst->solution, src->solution, J * M * 4, k, i);
+        row(dst_out->real_obs, src_out->real_obs, J * 7 * 4, k, i);
+        row(dst_out->action_mask, src_out->action_mask, J + 1, k, i);
+        row(dst_out->reward, src_out->reward, 4, k, i);
+        row(dst_out->done, src_out->done, 1, k, i);
+        row(dst_out->makespan, src_out->makespan, 4, k, i);
+        if (mode == 1) row(dst_tables->table_of_env, sd.table_of_env, 4, k, i);
+        if (mode == 2) {
+            row(dst_tables->ops, sd.ops, J * M * 4, k, i);
+            row(dst_tables->rem, sd.rem, J * M * 4, k, i);
+            row(dst_tables->inst, sd.inst, JSS_NI * 4, k, i);
+            dst->env_const[(size_t)k * JSS_NC + JSS_C_TABLE] = k;   // env i's table is table k now
+        }
+    };
+#ifdef _OPENMP
+    if (dd.threads > 0) {
+#pragma omp parallel for schedule(static) num_threads(dd.threads)
+        for (int k = 0; k < dd.batch; ++k) one(k);
+    } else {
+#pragma omp parallel for schedule(static)
+        for (int k = 0; k < dd.batch; ++k) one(k);
+    }
+#else
+    for (int k = 0; k < dd.batch; ++k) one(k);
 #endif
     return 0;
 }

@@ -5,6 +5,7 @@
 //   jss_wave_env.hpp    one wavefront per env        (any J <= 128, M <= 64)
 //   jss_packed_env.hpp  64/G envs per wavefront      (J, M <= G, G = 16 or 32)
 //   jss_generate.hpp    Taillard instances drawn into the envs' own tables (jss_generate)
+//   jss_clone.hpp       env k <- a copy of env src_of_dst[k], state, outputs and instance assignment (jss_clone)
 //
 // No MFMA anywhere: the path is integer indexing, there is no dense contraction.
 #include <mutex>
@@ -14,6 +15,7 @@
 #include "jss_packed_env.hpp"
 #include "jss_wave_env.hpp"
 #include "jss_generate.hpp"
+#include "jss_clone.hpp"
 
 namespace {
 using namespace jss;
@@ -589,6 +591,39 @@ int check_generate(const JssDesc *d, const JssState *s, const JssGen *g) {
     return 0;
 }
 
+// jss_clone's table kind of a batch: 0 one shared table, 1 table_of_env, 2 one table per env, 3 one env on one table (either
+// of 0 and 2)
+int clone_table_kind(const JssDesc *d) {
+    if (d->table_of_env) return 1;
+    if (d->n_tables == 1) return d->batch == 1 ? 3 : 0;
+    return 2;                                                              // n_tables == batch (check_args)
+}
+
+// jss_clone's argument checks (include/jss_hip.h); *mode: what of the instance assignment is copied -- 0 nothing (the
+// shared table), 1 the table_of_env entry, 2 the env's own op / work / instance table rows
+int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout, const JssCloneDst *dt, const JssDesc *sd,
+                const JssState *ss, const JssOut *sout, const int32_t *src_of_dst, int *mode) {
+    if (!src_of_dst) return JSS_E_NULL;
+    int rc = check_args(dd, ds, dout, true);
+    if (!rc) rc = check_args(sd, ss, sout, true);
+    if (rc) return rc;
+    if (dd->jmax != sd->jmax || dd->mmax != sd->mmax || record_ints_of(*dd) != record_ints_of(*sd)) return JSS_E_SHAPE;
+    const int a = clone_table_kind(dd), b = clone_table_kind(sd);
+    if (a == 1 || b == 1) {
+        if (a != b || dd->n_tables != sd->n_tables) return JSS_E_SHAPE;
+        *mode = 1;
+    } else if (a == 0 || b == 0) {
+        if (a == 2 || b == 2) return JSS_E_SHAPE;                           // (both have the one table)
+        *mode = 0;
+    } else {
+        *mode = 2;
+    }
+    if (*mode == 1 && (!dt || !dt->table_of_env)) return JSS_E_SHAPE;
+    if (*mode == 2 && (!dt || !dt->ops || !dt->rem || !dt->inst)) return JSS_E_SHAPE;
+    if (*mode == 2 && !sd->rem) return JSS_E_NULL;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1019,6 +1054,52 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
     const long long waves = ((long long)desc->batch + g.per_wave - 1) / g.per_wave;
     const int blocks = (int)((waves + kGenBlock / kWave - 1) / (kGenBlock / kWave));
     hipLaunchKernelGGL(jss_generate_kernel, dim3(blocks), dim3(kGenBlock), 0, reinterpret_cast<hipStream_t>(stream), g);
+    return (int)hipGetLastError();
+}
+
+// env k <- env src_of_dst[k] (jss_clone.hpp): one wavefront per destination env, one kernel argument per copied tensor
+int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,
+              const JssDesc *src_desc, const JssState *src, const JssOut *src_out, const int32_t *src_of_dst, void *stream) {
+    int mode = 0;
+    const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode);
+    if (rc) return rc;
+    if (dst_desc->batch == 0) return 0;
+    const long long J = dst_desc->jmax, M = dst_desc->mmax, R = record_ints_of(*dst_desc);
+    CloneParams p = {};
+    // dwordx4 where both rows of every env are 16-byte aligned (row length and both bases), else dwords, else bytes
+    auto add = [&](void *d, const void *s, long long bytes) {
+        CloneSeg &g = p.seg[p.n_seg++];
+        const uintptr_t a = (uintptr_t)d | (uintptr_t)s | (uintptr_t)bytes;
+        g.dst = static_cast<char *>(d);
+        g.src = static_cast<const char *>(s);
+        g.bytes = (int32_t)bytes;
+        g.unit = a % 16 == 0 ? 16 : a % 4 == 0 ? 4 : 1;
+        g.n = (int32_t)(bytes / g.unit);
+    };
+    add(dst->env, src->env, JSS_NH * 4);
+    add(dst->env_const, src->env_const, JSS_NC * 4);
+    add(dst->job, src->job, J * R * 4);
+    if (R == JSS_NF) add(dst->machine, src->machine, M * 4);
+    add(dst->solution, src->solution, J * M * 4);
+    add(dst_out->real_obs, src_out->real_obs, J * 7 * 4);
+    add(dst_out->action_mask, src_out->action_mask, J + 1);
+    add(dst_out->reward, src_out->reward, 4);
+    add(dst_out->done, src_out->done, 1);
+    add(dst_out->makespan, src_out->makespan, 4);
+    if (mode == 1) add(dst_tables->table_of_env, src_desc->table_of_env, 4);
+    if (mode == 2) {
+        add(dst_tables->ops, src_desc->ops, J * M * 4);
+        add(dst_tables->rem, src_desc->rem, J * M * 4);
+        add(dst_tables->inst, src_desc->inst, JSS_NI * 4);
+    }
+    p.own_tables = mode == 2;
+    p.src_of_dst = src_of_dst;
+    p.dst_env = dst->env;
+    p.batch_dst = dst_desc->batch;
+    p.batch_src = src_desc->batch;
+    const int per_block = kCloneBlock / kWave;
+    const int blocks = (int)(((long long)dst_desc->batch + per_block - 1) / per_block);
+    hipLaunchKernelGGL(jss_clone_kernel, dim3(blocks), dim3(kCloneBlock), 0, reinterpret_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
 }
 

@@ -49,7 +49,7 @@ class BatchedJssEnv:
     def __init__(self, instances, batch: Optional[int] = None, device=None, env_id_base: int = 0,
                  table_of_env: Optional[Sequence[int]] = None, seed: int = 0, kernel: Optional[str] = None,
                  compact: Optional[bool] = None, host_arena: bool = False, records: Optional[str] = None,
-                 order: Optional[str] = None, _backend=None, _generated=None):
+                 order: Optional[str] = None, _backend=None, _generated=None, _tables=None):
         self._owns_backend = _backend is None
         self.backend = be = _backend if _backend is not None else make_backend(device)
         if isinstance(instances, PackedBatch):
@@ -138,7 +138,9 @@ class BatchedJssEnv:
         self.fresh = bool(_generated["fresh"]) if _generated else False
         with be.on_device():
             # instance tables
-            if _generated:
+            if _tables is not None:                    # (fork: the parent's tensors, or tables of its own the clone fills)
+                self._ops, self._rem, self._inst = _tables
+            elif _generated:
                 self._ops, self._rem = be.zeros(pk.ops.shape, "int32"), be.zeros(pk.ops.shape, "int32")
                 self._inst = be.zeros(pk.inst.shape, "int32")
             else:
@@ -200,7 +202,8 @@ class BatchedJssEnv:
         if _generated:
             self._gen_struct = _abi.JssGen(p(self._ops), p(self._rem), p(self._inst), None, None, None, 0, _generated["jobs"],
                                            _generated["machines"], *_generated["durations"])
-            self.generate()                    # (derived seeds: the instance the first reset starts)
+            if _tables is None:
+                self.generate()                # (derived seeds: the instance the first reset starts)
 
     @classmethod
     def generated(cls, jobs: int, machines: int, batch: int, device=None, durations=(1, 99), instance_seed: int = 0,
@@ -424,6 +427,177 @@ class BatchedJssEnv:
         self._desc.env_ids = self.backend.ptr(self._env_ids)
         if self._classes is not None:
             self._build_class_views()                        # the class views carry their own (offset) copy of the pointer
+
+    # -- clones for search: fork / copy_from (jss_clone) ----------------------------------------------------------------
+    def _table_kind(self) -> str:
+        """How the envs reach their instance: "shared" (one table), "env_map" (table_of_env) or "own" (one table per env:
+        generated and per-env batches)."""
+        if self._table_of_env is not None:
+            return "env_map"
+        return "own" if (self._gen or self.n_tables > 1) else "shared"
+
+    def _index_arg(self, index, n_src, allow_skip):
+        """(device-side int32 index or None, host copy or None): a device tensor stays where it is (no host copy); anything
+        else is checked on the host -- every entry in [0, n_src), or -1 where allowed."""
+        be = self.backend
+        if getattr(be, "name", "") == "hip" and isinstance(index, be.torch.Tensor) and index.device.type == "cuda":
+            if index.dim() != 1 or index.dtype.is_floating_point or index.dtype == be.torch.bool:
+                raise ValueError("the index must be a 1-d integer tensor")
+            return index, None
+        a = np.asarray(index)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("the index must be a 1-d sequence of integers")
+        a = a.astype(np.int64)
+        low = -1 if allow_skip else 0
+        if a.size and (a.min() < low or a.max() >= n_src):
+            raise ValueError(f"index entries must lie in [{low}, {n_src})")
+        return None, a.astype(np.int32)
+
+    @staticmethod
+    def _shape_classes(jobs, machines, jmax):
+        """shape class of every (J, M) pair, as the constructor deals a by-shape batch"""
+        jobs, machines = np.asarray(jobs), np.asarray(machines)
+        wide = 63 if jmax > 64 else 64
+        return np.where((jobs <= 16) & (machines <= 16), 0, np.where((jobs <= 32) & (machines <= 32), 1,
+                                                                     np.where(jobs <= wide, 2, 3)))
+
+    def fork(self, index, env_id_base: int = 0) -> "BatchedJssEnv":
+        """A new batch of ``len(index)`` envs, env k a copy of env ``index[k]`` of this batch (``jss_clone``: state, last
+        outputs and instance assignment, byte for byte -- include/jss_hip.h says what is copied).  The fork takes this
+        batch's backend, seed, kernel and record layout and shares its instance tensors; a generated or per-env batch gives
+        the fork tables of its own, filled by the clone (a generated fork keeps the generator settings and ``fresh``).
+        Counters start at zero, and the fork's envs have the global ids ``env_id_base + k``: the random draws of a clone
+        differ from its parent's from here on.  A fork of a by-shape batch stays by shape when its envs' classes come out
+        in class order, else it runs on the padded extents' kernel.  ``index``: a host sequence or a device int tensor (one
+        device -> host copy when a host mirror has to follow it)."""
+        self._no_open_session("fork")
+        idx_dev, idx = self._index_arg(index, self.batch, allow_skip=False)
+        kind = self._table_kind()
+        if idx is None and (kind == "env_map" or (kind == "own" and not self._gen)):   # host mirrors follow the index
+            idx = self.backend.numpy(idx_dev).astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.batch):
+                raise ValueError(f"index entries must lie in [0, {self.batch})")
+            idx = idx.astype(np.int32)
+        n = int(idx_dev.shape[0]) if idx is None else int(idx.size)
+        if n < 1:
+            raise ValueError("a fork needs at least one env")
+        if self.medium and kind == "own" and n == 1:
+            raise ValueError("medium job records need at least two tables: fork at least two envs of this batch")
+        be = self.backend
+        records = "compact" if self.compact else "medium" if self.medium else "full"
+        pk, toe, gen, tables = self.packed if kind != "own" else None, None, None, None
+        if kind == "shared" or kind == "env_map":
+            tables = (self._ops, self._rem, self._inst)
+            toe = None if kind == "shared" else self.table_of_env_host[idx]
+        else:
+            with be.on_device():
+                tables = (be.zeros((n, self.jmax, self.mmax), "int32"), be.zeros((n, self.jmax, self.mmax), "int32"),
+                          be.zeros((n, _abi.NI), "int32"))
+            if self._gen:
+                gen = dict(self._gen)
+                z, full = np.zeros((), dtype=np.int32), (lambda v: np.full(n, v, dtype=np.int32))
+                pk = PackedBatch(ops=np.broadcast_to(z, (n, self.jmax, self.mmax)), rem=np.broadcast_to(z, (n, self.jmax, self.mmax)),
+                                 inst=np.broadcast_to(z, (n, _abi.NI)), jobs=full(gen["jobs"]), machines=full(gen["machines"]),
+                                 max_time_op=full(0), max_time_jobs=full(0), sum_op=full(0), jmax=self.jmax, mmax=self.mmax)
+            else:
+                src = self.packed
+                pk = PackedBatch(ops=src.ops[idx], rem=src.rem[idx], inst=src.inst[idx], jobs=src.jobs[idx],
+                                 machines=src.machines[idx], max_time_op=src.max_time_op[idx],
+                                 max_time_jobs=src.max_time_jobs[idx], sum_op=src.sum_op[idx], jmax=self.jmax, mmax=self.mmax)
+        f = BatchedJssEnv(pk, batch=n, env_id_base=env_id_base, table_of_env=toe, seed=self.seed, kernel=self.kernel,
+                          records=records, order="interleaved", _backend=be, _generated=gen, _tables=tables)
+        f.instances = self.instances if kind != "own" else None
+        if self._classes is not None:
+            cls = self._class_of_table[f.table_of_env_host]
+            if (np.diff(cls) >= 0).all():                     # classes in class order: the fork keeps the class bodies
+                f._class_of_table, f.order, f._order_given = self._class_of_table, "by_shape", self._order_given
+                f._build_class_views()
+        f._clone_from(self, idx_dev if idx_dev is not None else idx)
+        return f
+
+    def copy_from(self, src: "BatchedJssEnv", index):
+        """In place: env k <- env ``index[k]`` of ``src`` (``jss_clone``), ``-1`` leaves env k as it is.  ``src`` must have this
+        batch's layout and tables (a fork, the parent, or a batch on equal instances), else ``ValueError`` before anything is
+        launched.  ``src is self`` needs a host index whose source and destination envs are disjoint (a slot pool).  A
+        by-shape batch keeps every env in its shape class (checked on the host).  ``index``: a host sequence, or a device int
+        tensor -- whose entries outside [-1, src.batch) set ``ERR_BAD_INDEX`` in the env's status (the env is left as it was)."""
+        if not isinstance(src, BatchedJssEnv):
+            raise ValueError("copy_from needs a BatchedJssEnv to copy from")
+        self._no_open_session("copy_from")
+        src._no_open_session("copy_from")
+        be = self.backend
+        if getattr(be, "name", None) != getattr(src.backend, "name", None) or \
+                str(getattr(be, "device", "")) != str(getattr(src.backend, "device", "")):
+            raise ValueError("copy_from: source and destination live on different devices (cross-device copies are not supported)")
+        if (self.jmax, self.mmax, self.record_ints) != (src.jmax, src.mmax, src.record_ints):
+            raise ValueError("copy_from: the batches differ in padded extents or job-record layout")
+        kind = self._table_kind()
+        if kind != src._table_kind():
+            raise ValueError(f"copy_from: the batches reach their instances differently ({kind} vs {src._table_kind()})")
+        if kind != "own" and self._ops is not src._ops:
+            a, b = self.packed, src.packed
+            if not (np.array_equal(a.ops, b.ops) and np.array_equal(a.rem, b.rem) and np.array_equal(a.inst, b.inst)):
+                raise ValueError("copy_from: the batches run on different instance tables")
+        if kind == "own" and bool(self._gen) != bool(src._gen):
+            raise ValueError("copy_from: one of the batches is a generated batch, the other is not")
+        idx_dev, idx = self._index_arg(index, src.batch, allow_skip=True)
+        n = int(idx_dev.shape[0]) if idx is None else int(idx.size)
+        if n != self.batch:
+            raise ValueError(f"the index must hold one entry per env of this batch ({self.batch})")
+        if src is self:
+            if idx is None:
+                raise ValueError("copy_from(self, ...) needs a host index (its source and destination envs must be disjoint)")
+            dst = np.flatnonzero(idx >= 0)
+            if np.intersect1d(dst, idx[dst]).size:
+                raise ValueError("copy_from(self, ...): an env is both read and written -- source and destination envs must be disjoint")
+        follow = kind == "env_map" or (kind == "own" and not self._gen) or self._classes is not None
+        if idx is None and follow:                            # a host mirror follows: one device -> host copy of the index
+            idx = be.numpy(idx_dev).astype(np.int32)
+        if self._classes is not None:
+            ok = idx >= 0
+            mine = self._class_of_table[self.table_of_env_host[ok]]
+            theirs = self._shape_classes(src.jobs_per_env[idx[ok]], src.machines_per_env[idx[ok]], src.jmax)
+            if not np.array_equal(mine, theirs):
+                raise ValueError("order='by_shape': an env keeps its shape class for life -- copy envs of the same class into it")
+        self._clone_from(src, idx_dev if idx_dev is not None else idx, host_idx=idx)
+
+    def _clone_from(self, src, index, host_idx=None):
+        """jss_clone(self <- src, index) and the host mirrors that follow it (`host_idx`: the index on the host, when known)"""
+        be = self.backend
+        p = be.ptr
+        with be.on_device():
+            w = self._stage(self._act_in, index, "int32")
+            dt = _abi.JssCloneDst(p(self._table_of_env), p(self._ops), p(self._rem), p(self._inst))
+            rc = be.lib.jss_clone(C.byref(self._desc), C.byref(self._state), C.byref(self._out), C.byref(dt),
+                                  C.byref(src._desc), C.byref(src._state), C.byref(src._out), p(w), be.stream())
+        _abi.check(be.lib, rc, "jss_clone")
+        self._clone_keep = w                       # alive until the launch has read it
+        if host_idx is None and isinstance(index, np.ndarray):
+            host_idx = index
+        if host_idx is not None:
+            k = np.flatnonzero((host_idx >= 0) & (host_idx < src.batch))
+            i = host_idx[k]
+            kind = self._table_kind()
+            if kind == "env_map":
+                self.table_of_env_host = self.table_of_env_host.copy()
+                self.table_of_env_host[k] = src.table_of_env_host[i]
+            elif kind == "own" and not self._gen and k.size:
+                a, b = self.packed, src.packed
+                rows = {f: getattr(a, f).copy() for f in ("ops", "rem", "inst", "jobs", "machines", "max_time_op",
+                                                          "max_time_jobs", "sum_op")}
+                for f, v in rows.items():
+                    v[k] = getattr(b, f)[i]
+                self.packed = PackedBatch(jmax=self.jmax, mmax=self.mmax, **rows)
+            if kind != "shared":
+                jobs, machines = self.jobs_per_env.copy(), self.machines_per_env.copy()
+                jobs[k], machines[k] = src.jobs_per_env[i], src.machines_per_env[i]
+                changed = not (np.array_equal(jobs, self.jobs_per_env) and np.array_equal(machines, self.machines_per_env))
+                self.jobs_per_env, self.machines_per_env = jobs, machines
+                if changed and self._classes is not None:
+                    self._build_class_views()         # a class's smallest J / extents may have changed
+        if self._gen:
+            self._packed_stale = True
+        self._is_reset = self._is_reset or src._is_reset
 
     # -- raw ABI handles (bench.py launches through these) -------------------------------
     @property

@@ -323,6 +323,27 @@ class JssEnv(gymnasium_base("Env")):
         """gymnasium.Env.close(): waits for the env's outstanding device work."""
         self._b.synchronize()
 
+    def __deepcopy__(self, memo):
+        """``copy.deepcopy(env)`` as with the reference's plain Python object (MCTS / search code clones envs mid-episode):
+        a new env on the same instance and device whose state is this env's, cloned on the device (``jss_clone``), plus the
+        host-side attributes.  The two are independent from then on: closing or stepping one leaves the other as it was.
+        The copy has this env's env id and seed, so a random rollout of the copy draws what this env's would."""
+        b = self._b
+        be = b.backend
+        # an env that owns its backend gets a copy with a backend of its own (same device); a borrowed one is shared
+        device = "cpu" if getattr(be, "name", "") == "cpu" else str(getattr(be, "device", None))
+        new = type(self)(env_config={"instance_path": self.instance}, device=device if b._owns_backend else None,
+                         _backend=None if b._owns_backend else be)
+        memo[id(self)] = new
+        new._b.seed = b.seed
+        new._b.copy_from(b, [0])
+        new._alloc_log, new._alloc_log_ok = list(self._alloc_log), self._alloc_log_ok
+        new.last_time_step = self.last_time_step
+        new.last_solution = None if self.last_solution is None else np.array(self.last_solution, copy=True)
+        new.colors = list(self.colors)
+        new.start_timestamp = self.start_timestamp
+        return new
+
     def _run_rule(self, kind, explore: float = 0.0, seed=None):
         """One whole episode of a dispatching rule, rule + step fused on the device (dispatching.py:55-75 with the
         exploration drawn from the counter RNG).  Returns (total reward, makespan) like ``run_episode``."""
