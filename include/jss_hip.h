@@ -54,7 +54,9 @@
  *     DEVICE pointer owned by the caller (the Python host allocates them as torch
  *     tensors).  The library never allocates, frees or synchronises.
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*).
- *   - return value: 0 = launched, <0 = argument error (JSS_E_*), >0 = hipError_t.
+ *   - return value: 0 = launched, <0 = argument error (JSS_E_*), >0 = hipError_t.  Both libraries check arguments through
+ *     the same code (jssenv_amd/csrc/jss_abi_checks.hpp) before they do anything else: an argument error touches nothing,
+ *     multi-set calls included, and never depends on the library (JSS_E_LDS and JSS_E_RESIDENT aside: launch limits).
  *   - kernels: when every env of the batch has jobs, machines <= 32, 64/G envs share a
  *     wavefront (G = 16 or 32 lanes per env); otherwise one wavefront simulates one env
  *     (job j on lane j % 64, slot j / 64; machine m on lane m).  Limits: jobs <= 128,

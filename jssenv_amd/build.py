@@ -19,6 +19,7 @@ CPU_SRC = os.path.join(_HERE, "csrc", "jss_cpu.cpp")
 CPU_OUT = os.path.join(_HERE, "libjss_cpu.so")
 CPU_FLAGS = ["-O3", "-std=c++17", "-fopenmp", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(_ROOT, "include")]
 _HEADER = os.path.join(_ROOT, "include", "jss_hip.h")
+_CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 
 
 def hipcc() -> str:
@@ -42,7 +43,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _HEADER]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _HEADER]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -5,7 +5,9 @@
 // the simulator: scalar C++ working in place on the 32-byte job records, OpenMP over envs.  It exists for
 // BASELINE config 1 ("runs without a GPU"), for `device="cpu"` users of the package, and as the multi-core
 // CPU baseline bench.py times next to the GPU (cpu_baseline kind "twin").  It shares no code with oracle/
-// (the literal restatement of the reference used as the checker) -- tests/ compares the two.
+// (the literal restatement of the reference used as the checker) -- tests/ compares the two.  With libjss_hip.so it
+// shares exactly one file, jss_abi_checks.hpp: the argument checks every entry point starts with, so that the two
+// libraries answer a bad argument list with the same code and touch nothing (tests/test_abi_arguments.py).
 //
 // Reference semantics (JSSEnv/envs/jss_env.py, cited per function) in the queue-free form: the reference's
 // sorted event list is {t + tm[m] : tm[m] > 0}, its M x J illegal_actions matrix is blocked[j] && need[j] == m,
@@ -17,9 +19,10 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "jss_hip.h"
+#include "jss_abi_checks.hpp"
 
 namespace {
+using namespace jss_abi;
 
 constexpr int kBig = 0x3fffffff;
 constexpr int kDurMask = 0xffff;
@@ -762,96 +765,10 @@ int run(const Call &c, int mode) {
     return 0;
 }
 
-int check_args(const JssDesc *d, const JssState *s, const JssOut *o, bool need_out) {
-    if (!d || !s) return JSS_E_NULL;
-    if (!d->ops || !d->inst) return JSS_E_NULL;
-    if (!s->env || !s->env_const || !s->job || !s->solution) return JSS_E_NULL;
-    if (!s->machine && d->record_ints != JSS_NFC && d->record_ints != JSS_NFM) return JSS_E_NULL;   // compact / medium batches keep no machine clocks
-    if (need_out && (!o || !o->real_obs || !o->action_mask || !o->reward || !o->done || !o->makespan)) return JSS_E_NULL;
-    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 2 || d->mmax > JSS_MAX_MACHINES ||
-        d->n_tables < 1)
-        return JSS_E_SHAPE;
-    if (!d->table_of_env && d->n_tables != 1 && d->n_tables != d->batch) return JSS_E_SHAPE;
-    if (d->kernel & ~(JSS_KERNEL_WAVE | JSS_KERNEL_ONE_ENV_PER_WAVE | JSS_KERNEL_TWO_ENVS_PER_WAVE)) return JSS_E_KIND;
-    if (d->record_ints != 0 && d->record_ints != JSS_NF && d->record_ints != JSS_NFC && d->record_ints != JSS_NFM) return JSS_E_SHAPE;
-    if (d->record_ints == JSS_NFC && d->n_tables != 1) return JSS_E_SHAPE;
-    if (d->record_ints == JSS_NFM && (d->mmax > 32 || d->n_tables == 1)) return JSS_E_SHAPE;
-    return 0;
-}
-
-// f64_ok: the calls whose policy is a launch of its own on the GPU (JSS_POLICY_CR_F64, include/jss_hip.h): same answers here
-int check_kind(const JssDesc *d, int kind_arg, bool f64_ok = false) {
-    const int kind = kind_arg & 0xFF, fp = (kind_arg >> 8) & 0xFF, fq = (kind_arg >> 16) & 0xFF;
-    if (kind_arg < 0 || (kind_arg >> 25) || kind >= JSS_N_POLICIES) return JSS_E_KIND;
-    if ((kind_arg >> 24) & 1) {
-        if (!f64_ok || kind != JSS_POLICY_CR || fp || fq || !(d->cr_factor > 0.0) || !(d->cr_factor < 1e300)) return JSS_E_KIND;
-    }
-    if (fp || fq) {                                  // a due-date factor p / q: CriticalRatio only, q a power of two <= 64
-        if (kind != JSS_POLICY_CR || fp < 1 || fq < 1 || fq > 64 || (fq & (fq - 1))) return JSS_E_KIND;
-    }
-    if ((kind == JSS_POLICY_MWR || kind == JSS_POLICY_LWR || kind == JSS_POLICY_CR) && !d->rem) return JSS_E_NULL;
-    return 0;
-}
-
-// jss_step_logits' checks of a JssLogits against its set's description
-int check_logits(const JssDesc *d, const JssLogits *lg) {
-    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
-    if (lg->row != 0 && lg->row < (int64_t)d->jmax + 1) return JSS_E_SHAPE;
-    if (lg->row > (1 << 24)) return JSS_E_SHAPE;
-    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
-    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
-    return 0;
-}
-
-// jss_clone (include/jss_hip.h): env k <- env src_of_dst[k], row by row.  The table kind of a batch: 0 one shared table,
-// 1 table_of_env, 2 one table per env, 3 one env on one table (either of 0 and 2)
-int clone_table_kind(const JssDesc *d) {
-    if (d->table_of_env) return 1;
-    if (d->n_tables == 1) return d->batch == 1 ? 3 : 0;
-    return 2;
-}
-
-int clone_record_ints(const JssDesc *d) { return d->record_ints == JSS_NFC || d->record_ints == JSS_NFM ? d->record_ints : JSS_NF; }
-
-// *mode: 0 no instance assignment to copy, 1 the table_of_env entry, 2 the env's own table rows
-int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout, const JssCloneDst *dt, const JssDesc *sd,
-                const JssState *ss, const JssOut *sout, const int32_t *src_of_dst, int *mode) {
-    if (!src_of_dst) return JSS_E_NULL;
-    int rc = check_args(dd, ds, dout, true);
-    if (!rc) rc = check_args(sd, ss, sout, true);
-    if (rc) return rc;
-    if (dd->jmax != sd->jmax || dd->mmax != sd->mmax || clone_record_ints(dd) != clone_record_ints(sd)) return JSS_E_SHAPE;
-    const int a = clone_table_kind(dd), b = clone_table_kind(sd);
-    if (a == 1 || b == 1) {
-        if (a != b || dd->n_tables != sd->n_tables) return JSS_E_SHAPE;
-        *mode = 1;
-    } else if (a == 0 || b == 0) {
-        if (a == 2 || b == 2) return JSS_E_SHAPE;
-        *mode = 0;
-    } else {
-        *mode = 2;
-    }
-    if (*mode == 1 && (!dt || !dt->table_of_env)) return JSS_E_SHAPE;
-    if (*mode == 2 && (!dt || !dt->ops || !dt->rem || !dt->inst)) return JSS_E_SHAPE;
-    if (*mode == 2 && !sd->rem) return JSS_E_NULL;
-    return 0;
-}
-
 // jss_generate (include/jss_hip.h): a Taillard instance into env b's own tables, the draws of the two Lehmer streams walked
 // in order -- the same double arithmetic as the host generator and the kernel, the same float32 reciprocals
 constexpr int64_t kLcgM = 2147483647;
 constexpr uint64_t kGenSeedXor = JSS_GEN_SEED_XOR;
-
-int check_generate(const JssDesc *d, const JssState *s, const JssGen *g) {
-    if (!d || !g || !g->ops || !g->rem || !g->inst) return JSS_E_NULL;
-    if (!g->time_seed != !g->machine_seed) return JSS_E_NULL;
-    if (!g->time_seed && (!s || !s->env)) return JSS_E_NULL;
-    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 1 || d->mmax > JSS_MAX_MACHINES) return JSS_E_SHAPE;
-    if (d->n_tables != d->batch || d->table_of_env) return JSS_E_SHAPE;
-    if (g->jobs < 1 || g->jobs > d->jmax || g->machines < 1 || g->machines > d->mmax) return JSS_E_SHAPE;
-    if (g->dur_low < 1 || g->dur_low > g->dur_high || g->dur_high > 0xFFFF) return JSS_E_SHAPE;
-    return 0;
-}
 
 int lcg_unif(int64_t &x, int low, int n) {
     x = x * 16807 % kLcgM;
@@ -933,39 +850,26 @@ const char *jss_backend(void) {
 }
 
 const char *jss_error_string(int code) {
-    switch (code) {
-    case 0: return "ok";
-    case JSS_E_NULL: return "null pointer in JssDesc/JssState/JssOut or arguments";
-    case JSS_E_SHAPE: return "bad shape (batch/jmax/mmax/n_tables/n_sub)";
-    case JSS_E_KIND: return "unknown policy kind or kernel flavour";
-    case JSS_E_LDS: return "batch shape needs more LDS per workgroup than the device provides";
-    case JSS_E_RESIDENT: return "the batch does not fit the chip as one round of resident workgroups (step session)";
-    case JSS_E_SESSION: return "step session: bad step range (mailbox ring overrun, or the session was never opened)";
-    default: return "unknown error";
-    }
+    const char *text = arg_error_string(code);
+    return text ? text : "unknown error";
 }
 
 int jss_reset(const JssDesc *desc, const JssState *state, const JssOut *out, const uint8_t *which, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
+    if (const int rc = check_reset(desc, state, out)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.which = which;
     return run(c, kReset);
 }
 
 int jss_step(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_step(desc, state, actions, out)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.actions = actions;
     return run(c, kStep);
 }
 
 int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_step(desc, state, actions, out)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.actions = actions; c.flags = JSS_ROLLOUT_AUTORESET;
     return run(c, kStep);
@@ -973,9 +877,7 @@ int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t
 
 int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
                     const JssOut *out, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_logits(desc, lg))) return rc;
+    if (const int rc = check_step_logits(desc, state, lg, out)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.lg = *lg; c.seed = seed; c.flags = flags & JSS_ROLLOUT_AUTORESET;
     if (c.lg.row == 0) c.lg.row = desc->jmax + 1;
@@ -983,8 +885,7 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
 }
 
 int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which, int32_t *hole, const JssOut *out, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
+    if (const int rc = check_reset(desc, state, out)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.which = which; c.hole = hole;
     return run(c, kAdvance);
@@ -992,10 +893,7 @@ int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which
 
 int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t seed, uint32_t explore_q16, int32_t *actions,
                void *) {
-    int rc = check_args(desc, state, nullptr, false);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
-    if ((rc = check_kind(desc, kind, true))) return rc;
+    if (const int rc = check_policy(desc, state, kind, actions)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16;
     return run(c, kPolicy);
@@ -1003,10 +901,7 @@ int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t se
 
 int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed, uint32_t explore_q16,
                 int32_t n_iter, int32_t flags, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_kind(desc, kind))) return rc;
-    if (n_iter < 0) return JSS_E_SHAPE;
+    if (const int rc = check_rollout(desc, state, out, kind, n_iter)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16;
     c.n_iter = n_iter; c.flags = flags;
@@ -1015,11 +910,7 @@ int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, i
 
 int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, int kind,
                    uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!traj) return JSS_E_NULL;
-    if ((rc = check_kind(desc, kind))) return rc;
-    if (n_steps < 0) return JSS_E_SHAPE;
+    if (const int rc = check_trajectory(desc, state, out, traj, kind, n_steps)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.t = *traj; c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16;
     c.n_iter = n_steps; c.flags = flags;
@@ -1028,11 +919,8 @@ int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out
 
 int jss_steps(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, const int32_t *actions,
               int32_t n_steps, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (n_steps < 0) return JSS_E_SHAPE;
-    if (n_steps == 0) return 0;                       // nothing to do (an empty action buffer has no address)
-    if (!actions) return JSS_E_NULL;
+    const int rc = check_steps(desc, state, out, actions, n_steps);
+    if (rc || n_steps == 0) return rc;                // (n_steps == 0: nothing to do)
     Call c;
     c.d = *desc; c.s = *state; c.o = *out; c.actions = actions; c.n_iter = n_steps;
     if (traj) c.t = *traj;
@@ -1053,24 +941,8 @@ struct HostSession {
 static std::mutex g_sessions_mutex;
 static std::unordered_map<const void *, HostSession> g_sessions;
 
-int jss_session_open(const JssDesc *desc, const JssState *state, const JssOut *out, const JssSession *session, void *) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!session || !session->mail || !session->progress || !session->status) return JSS_E_NULL;
-    if (session->depth < 1 || session->timeout_ms < 0 || desc->batch < 1) return JSS_E_SHAPE;
-    const int want = session->slots;
-    if (want != 0 && want != 1 && want != 2 && want != 4 && want != 8) return JSS_E_SHAPE;
-    std::lock_guard<std::mutex> lock(g_sessions_mutex);
-    g_sessions[session->progress] = HostSession{*desc, *state, *out, 0};
-    session->status[3] = want ? want : 1;
-    return 0;
-}
-
-int jss_session_post(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t first_step,
-                     int32_t n_steps, int32_t waited, void *) {
-    if (!desc || !session || !session->mail || !actions) return JSS_E_NULL;
-    if (first_step < 0 || n_steps < 1 || waited < 0 || waited > first_step || first_step + n_steps - waited > session->depth)
-        return JSS_E_SESSION;
+// post's steps, once the arguments are checked: the session must be open and first_step its next step (JSS_E_SESSION)
+static int post_steps(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t first_step, int32_t n_steps) {
     HostSession hs;
     {
         std::lock_guard<std::mutex> lock(g_sessions_mutex);
@@ -1092,9 +964,23 @@ int jss_session_post(const JssDesc *desc, const JssSession *session, const int32
     return 0;
 }
 
+int jss_session_open(const JssDesc *desc, const JssState *state, const JssOut *out, const JssSession *session, void *) {
+    if (const int rc = check_session_open(desc, state, out, session)) return rc;
+    const int want = session->slots;
+    std::lock_guard<std::mutex> lock(g_sessions_mutex);
+    g_sessions[session->progress] = HostSession{*desc, *state, *out, 0};
+    session->status[3] = want ? want : 1;
+    return 0;
+}
+
+int jss_session_post(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t first_step,
+                     int32_t n_steps, int32_t waited, void *) {
+    if (const int rc = check_session_post(desc, session, actions, first_step, n_steps, waited)) return rc;
+    return post_steps(desc, session, actions, first_step, n_steps);
+}
+
 int jss_session_wait(const JssDesc *desc, const JssSession *session, int32_t steps_done, void *) {
-    if (!desc || !session || !session->progress || !session->status) return JSS_E_NULL;
-    if (steps_done < 0) return JSS_E_SESSION;
+    if (const int rc = check_session_wait(desc, session, steps_done)) return rc;
     std::lock_guard<std::mutex> lock(g_sessions_mutex);
     const auto it = g_sessions.find(session->progress);
     if (it == g_sessions.end()) return JSS_E_SESSION;
@@ -1103,12 +989,12 @@ int jss_session_wait(const JssDesc *desc, const JssSession *session, int32_t ste
 }
 
 int jss_session_step(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t step, void *) {
-    return jss_session_post(desc, session, actions, step, 1, step, nullptr);
+    if (const int rc = check_session_step(desc, session, actions, step)) return rc;
+    return post_steps(desc, session, actions, step, 1);
 }
 
 int jss_session_close(const JssDesc *desc, const JssSession *session, int32_t next_step, void *) {
-    if (!desc || !session || !session->mail) return JSS_E_NULL;
-    if (next_step < 0) return JSS_E_SESSION;
+    if (const int rc = check_session_close(desc, session, next_step)) return rc;
     std::lock_guard<std::mutex> lock(g_sessions_mutex);
     g_sessions.erase(session->progress);
     session->status[2] += 1;
@@ -1121,12 +1007,8 @@ int jss_sync_check(void *) { return 0; }                                  // eve
 // rollout per env; sub-batches and streams have nothing to overlap here
 int jss_rollout_steps(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                       uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub, void *const *streams) {
-    if (n_steps < 0 || n_sub < 1 || n_sub > 16) return desc && state ? JSS_E_SHAPE : JSS_E_NULL;
-    if (!streams) return JSS_E_NULL;
-    if (n_steps == 0) {                               // no step: nothing is touched (the HIP library launches nothing); arguments checked
-        const int rc = check_args(desc, state, out, true);
-        return rc ? rc : check_kind(desc, kind);
-    }
+    const int rc = check_rollout_steps(desc, state, out, kind, n_steps, n_sub, streams);
+    if (rc || n_steps == 0) return rc;                // (no step: nothing is touched)
     return jss_rollout(desc, state, out, kind, seed, explore_q16, n_steps, flags, nullptr);
 }
 
@@ -1134,103 +1016,69 @@ int jss_rollout_steps(const JssDesc *desc, const JssState *state, const JssOut *
 int jss_policy_step_steps(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                           uint32_t explore_q16, int32_t *actions, int32_t n_steps, int32_t flags, int32_t n_sub,
                           void *const *streams) {
-    if (n_steps < 0 || n_sub < 1 || n_sub > 16) return desc && state ? JSS_E_SHAPE : JSS_E_NULL;
-    if (!streams || !actions) return JSS_E_NULL;
-    for (int s = 0; s < n_steps; ++s) {
-        int rc = jss_policy(desc, state, kind, seed, explore_q16, actions, nullptr);
+    int rc = check_policy_step_steps(desc, state, out, kind, actions, n_steps, n_sub, streams);
+    for (int s = 0; s < n_steps && !rc; ++s) {
+        rc = jss_policy(desc, state, kind, seed, explore_q16, actions, nullptr);
         if (!rc) rc = (flags & JSS_ROLLOUT_AUTORESET) ? jss_step_autoreset(desc, state, actions, out, nullptr)
                                                      : jss_step(desc, state, actions, out, nullptr);
-        if (rc) return rc;
     }
-    return 0;
+    return rc;
 }
 
 // several independent env sets: each is its own synchronous rollout here
 int jss_rollout_steps_multi(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
                             const JssOut *const *outs, int kind, uint64_t seed, uint32_t explore_q16, int32_t n_steps,
                             int32_t flags, void *const *streams) {
-    if (!descs || !states || !outs || !streams) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16 || n_steps < 0) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {
-        int rc = check_args(descs[i], states[i], outs[i], true);
-        if (!rc) rc = check_kind(descs[i], kind);
-        if (!rc && n_steps > 0)                       // (n_steps == 0: nothing is touched, like the HIP library, which launches nothing)
-            rc = jss_rollout(descs[i], states[i], outs[i], kind, seed, explore_q16, n_steps, flags & JSS_ROLLOUT_AUTORESET, nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_rollout_steps_multi(n_sets, descs, states, outs, kind, n_steps, streams);
+    for (int i = 0; i < n_sets && n_steps > 0 && !rc; ++i)
+        rc = jss_rollout(descs[i], states[i], outs[i], kind, seed, explore_q16, n_steps, flags & JSS_ROLLOUT_AUTORESET, nullptr);
+    return rc;
 }
 
-// several env sets per call (include/jss_hip.h jss_multi_*): the host twin has no launches to fuse -- set after set
+// several env sets per call (include/jss_hip.h jss_multi_*): the host twin has no launches to fuse -- every set is checked,
+// then the sets run one after the other
 int jss_multi_reset(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                     const uint8_t *const *which, void *stream) {
-    if (!descs || !states || !outs) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = jss_reset(descs[i], states[i], outs[i], which ? which[i] : nullptr, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_multi_reset(n_sets, descs, states, outs);
+    for (int i = 0; i < n_sets && !rc; ++i) rc = jss_reset(descs[i], states[i], outs[i], which ? which[i] : nullptr, stream);
+    return rc;
 }
 
 int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const int32_t *const *actions,
                    const JssOut *const *outs, int32_t flags, void *stream) {
-    if (!descs || !states || !outs || !actions) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = (flags & JSS_ROLLOUT_AUTORESET) ? jss_step_autoreset(descs[i], states[i], actions[i], outs[i], stream)
-                                                       : jss_step(descs[i], states[i], actions[i], outs[i], stream);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_multi_step(n_sets, descs, states, actions, outs);
+    for (int i = 0; i < n_sets && !rc; ++i)
+        rc = (flags & JSS_ROLLOUT_AUTORESET) ? jss_step_autoreset(descs[i], states[i], actions[i], outs[i], stream)
+                                             : jss_step(descs[i], states[i], actions[i], outs[i], stream);
+    return rc;
 }
 
 int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
                           const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream) {
-    if (!descs || !states || !outs || !lgs) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {               // every set checked first: an argument error steps no set (as the HIP library)
-        int rc = check_args(descs[i], states[i], outs[i], true);
-        if (!rc) rc = check_logits(descs[i], lgs[i]);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = jss_step_logits(descs[i], states[i], lgs[i], seed, flags, outs[i], stream);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_multi_step_logits(n_sets, descs, states, lgs, outs);
+    for (int i = 0; i < n_sets && !rc; ++i) rc = jss_step_logits(descs[i], states[i], lgs[i], seed, flags, outs[i], stream);
+    return rc;
 }
 
 int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, int kind, uint64_t seed,
                      uint32_t explore_q16, int32_t *const *actions, void *stream) {
-    if (!descs || !states || !actions) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = jss_policy(descs[i], states[i], kind, seed, explore_q16, actions[i], stream);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_multi_policy(n_sets, descs, states, kind, actions);
+    for (int i = 0; i < n_sets && !rc; ++i) rc = jss_policy(descs[i], states[i], kind, seed, explore_q16, actions[i], stream);
+    return rc;
 }
 
+// n_steps x rollout(n_iter = 1) == rollout(n_iter = n_steps) on the state; `out` holds the last step either way
 int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                       int kind, uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub,
                       void *const *streams) {
-    if (!descs || !states || !outs || !streams) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16 || n_steps < 0 || n_sub < 1 || n_sub > 16) return JSS_E_SHAPE;
-    void *stream = nullptr;
-    for (int i = 0; i < n_sets; ++i) {       // n_steps x rollout(n_iter = 1) == rollout(n_iter = n_steps) on the state; `out` holds the last step either way
-        int rc = check_args(descs[i], states[i], outs[i], true);
-        if (!rc) rc = check_kind(descs[i], kind);
-        if (!rc && n_steps > 0)                       // (n_steps == 0: nothing is touched, like the HIP library, which launches nothing)
-            rc = jss_rollout(descs[i], states[i], outs[i], kind, seed, explore_q16, n_steps, flags & JSS_ROLLOUT_AUTORESET, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = check_multi_rollout(n_sets, descs, states, outs, kind, n_steps, n_sub, streams);
+    for (int i = 0; i < n_sets && n_steps > 0 && !rc; ++i)
+        rc = jss_rollout(descs[i], states[i], outs[i], kind, seed, explore_q16, n_steps, flags & JSS_ROLLOUT_AUTORESET, nullptr);
+    return rc;
 }
 
 int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *) {
-    const int rc = check_generate(desc, state, gen);
-    if (rc) return rc;
+    if (const int rc = check_generate(desc, state, gen)) return rc;
     const JssDesc d = *desc;
     const JssGen g = *gen;
     const bool all = !which && !g.actions;
@@ -1254,10 +1102,9 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
 int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,
               const JssDesc *src_desc, const JssState *src, const JssOut *src_out, const int32_t *src_of_dst, void *) {
     int mode = 0;
-    const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode);
-    if (rc) return rc;
+    if (const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode)) return rc;
     const JssDesc dd = *dst_desc, sd = *src_desc;
-    const size_t J = dd.jmax, M = dd.mmax, R = clone_record_ints(&dd);
+    const size_t J = dd.jmax, M = dd.mmax, R = record_ints_of(dd);
     auto row = [](void *d, const void *s, size_t bytes, size_t k, size_t i) {
         std::memcpy(static_cast<char *>(d) + k * bytes, static_cast<const char *>(s) + i * bytes, bytes);
     };

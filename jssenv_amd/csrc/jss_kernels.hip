@@ -6,6 +6,7 @@
 //   jss_packed_env.hpp  64/G envs per wavefront      (J, M <= G, G = 16 or 32)
 //   jss_generate.hpp    Taillard instances drawn into the envs' own tables (jss_generate)
 //   jss_clone.hpp       env k <- a copy of env src_of_dst[k], state, outputs and instance assignment (jss_clone)
+//   jss_abi_checks.hpp  the C ABI's argument checks, shared with the host-core twin (jss_cpu.cpp)
 //
 // No MFMA anywhere: the path is integer indexing, there is no dense contraction.
 #include <mutex>
@@ -16,47 +17,15 @@
 #include "jss_wave_env.hpp"
 #include "jss_generate.hpp"
 #include "jss_clone.hpp"
+#include "jss_abi_checks.hpp"
 
 namespace {
 using namespace jss;
+using namespace jss_abi;
 
 // ---------------------------------------------------------------------------------------
 // host side of the C ABI
 // ---------------------------------------------------------------------------------------
-int check_args(const JssDesc *d, const JssState *s, const JssOut *o, bool need_out) {
-    if (!d || !s) return JSS_E_NULL;
-    if (!d->ops || !d->inst) return JSS_E_NULL;
-    if (!s->env || !s->env_const || !s->job || !s->solution) return JSS_E_NULL;
-    if (!s->machine && d->record_ints != JSS_NFC && d->record_ints != JSS_NFM) return JSS_E_NULL;   // compact / medium batches keep no machine clocks
-    if (need_out && (!o || !o->real_obs || !o->action_mask || !o->reward || !o->done || !o->makespan)) return JSS_E_NULL;
-    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 2 || d->mmax > JSS_MAX_MACHINES ||
-        d->n_tables < 1)
-        return JSS_E_SHAPE;
-    if (!d->table_of_env && d->n_tables != 1 && d->n_tables != d->batch) return JSS_E_SHAPE;
-    if (d->kernel & ~(JSS_KERNEL_WAVE | JSS_KERNEL_ONE_ENV_PER_WAVE | JSS_KERNEL_TWO_ENVS_PER_WAVE)) return JSS_E_KIND;
-    if (d->record_ints != 0 && d->record_ints != JSS_NF && d->record_ints != JSS_NFC && d->record_ints != JSS_NFM) return JSS_E_SHAPE;
-    if (d->record_ints == JSS_NFC && d->n_tables != 1) return JSS_E_SHAPE;   // compact records need the ONE table in LDS
-    // medium records: 21-bit ops (machines <= 32, whatever the number of jobs), per-env tables
-    if (d->record_ints == JSS_NFM && (d->mmax > 32 || d->n_tables == 1)) return JSS_E_SHAPE;
-    return 0;
-}
-
-int record_ints_of(const JssDesc &d) { return d.record_ints == JSS_NFC ? JSS_NFC : d.record_ints == JSS_NFM ? JSS_NFM : JSS_NF; }
-
-// f64_ok: the call's policy is a launch of its own (the kernels that carry JSS_POLICY_CR_F64's float64 selector)
-int check_kind(const JssDesc *d, int kind_arg, bool f64_ok = false) {
-    const int kind = kind_arg & 0xFF, fp = (kind_arg >> 8) & 0xFF, fq = (kind_arg >> 16) & 0xFF;
-    if (kind_arg < 0 || (kind_arg >> 25) || kind >= JSS_N_POLICIES) return JSS_E_KIND;
-    if ((kind_arg >> 24) & 1) {                      // JSS_POLICY_CR_F64: the factor is JssDesc.cr_factor
-        if (!f64_ok || kind != JSS_POLICY_CR || fp || fq || !(d->cr_factor > 0.0) || !(d->cr_factor < 1e300)) return JSS_E_KIND;
-    }
-    if (fp || fq) {                                  // a due-date factor p / q: CriticalRatio only, q a power of two <= 64
-        if (kind != JSS_POLICY_CR || fp < 1 || fq < 1 || fq > 64 || (fq & (fq - 1))) return JSS_E_KIND;
-    }
-    if ((kind == JSS_POLICY_MWR || kind == JSS_POLICY_LWR || kind == JSS_POLICY_CR) && !d->rem) return JSS_E_NULL;
-    return 0;
-}
-
 // Events of JSS_ROLLOUT_FORK_JOIN: one set per main stream (streams[0]), created on first use on the device that is
 // current then -- the device the caller launches on -- and kept for the life of the process.  Two env objects on two
 // devices, or two host threads driving two streams, never share an event; the registry itself is guarded by a mutex.
@@ -559,71 +528,6 @@ int launch_multi(Params *ps, int n, int n_steps, int n_sub, void *const *streams
     return rc ? rc : jrc;
 }
 
-// jss_step_logits' checks of a JssLogits against its set's description
-int check_logits(const JssDesc *d, const JssLogits *lg) {
-    if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
-    if (lg->row != 0 && lg->row < (int64_t)d->jmax + 1) return JSS_E_SHAPE;
-    if (lg->row > (1 << 24)) return JSS_E_SHAPE;                         // (lane offsets are 32-bit)
-    if (lg->dtype != JSS_LOGITS_F32 && lg->dtype != JSS_LOGITS_BF16) return JSS_E_KIND;
-    if (!(lg->temperature >= 0.f)) return JSS_E_KIND;                    // < 0 or NaN
-    return 0;
-}
-
-int check_multi(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs, bool need_out) {
-    if (!descs || !states || (need_out && !outs)) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16) return JSS_E_SHAPE;
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = check_args(descs[i], states[i], need_out ? outs[i] : nullptr, need_out);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// jss_generate's argument checks (include/jss_hip.h)
-int check_generate(const JssDesc *d, const JssState *s, const JssGen *g) {
-    if (!d || !g || !g->ops || !g->rem || !g->inst) return JSS_E_NULL;
-    if (!g->time_seed != !g->machine_seed) return JSS_E_NULL;                 // both seed arrays or neither
-    if (!g->time_seed && (!s || !s->env)) return JSS_E_NULL;                  // derived seeds read the episode
-    if (d->batch < 0 || d->jmax < 1 || d->jmax > JSS_MAX_JOBS || d->mmax < 1 || d->mmax > JSS_MAX_MACHINES) return JSS_E_SHAPE;
-    if (d->n_tables != d->batch || d->table_of_env) return JSS_E_SHAPE;        // table i is env i's alone
-    if (g->jobs < 1 || g->jobs > d->jmax || g->machines < 1 || g->machines > d->mmax) return JSS_E_SHAPE;
-    if (g->dur_low < 1 || g->dur_low > g->dur_high || g->dur_high > 0xFFFF) return JSS_E_SHAPE;
-    return 0;
-}
-
-// jss_clone's table kind of a batch: 0 one shared table, 1 table_of_env, 2 one table per env, 3 one env on one table (either
-// of 0 and 2)
-int clone_table_kind(const JssDesc *d) {
-    if (d->table_of_env) return 1;
-    if (d->n_tables == 1) return d->batch == 1 ? 3 : 0;
-    return 2;                                                              // n_tables == batch (check_args)
-}
-
-// jss_clone's argument checks (include/jss_hip.h); *mode: what of the instance assignment is copied -- 0 nothing (the
-// shared table), 1 the table_of_env entry, 2 the env's own op / work / instance table rows
-int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout, const JssCloneDst *dt, const JssDesc *sd,
-                const JssState *ss, const JssOut *sout, const int32_t *src_of_dst, int *mode) {
-    if (!src_of_dst) return JSS_E_NULL;
-    int rc = check_args(dd, ds, dout, true);
-    if (!rc) rc = check_args(sd, ss, sout, true);
-    if (rc) return rc;
-    if (dd->jmax != sd->jmax || dd->mmax != sd->mmax || record_ints_of(*dd) != record_ints_of(*sd)) return JSS_E_SHAPE;
-    const int a = clone_table_kind(dd), b = clone_table_kind(sd);
-    if (a == 1 || b == 1) {
-        if (a != b || dd->n_tables != sd->n_tables) return JSS_E_SHAPE;
-        *mode = 1;
-    } else if (a == 0 || b == 0) {
-        if (a == 2 || b == 2) return JSS_E_SHAPE;                           // (both have the one table)
-        *mode = 0;
-    } else {
-        *mode = 2;
-    }
-    if (*mode == 1 && (!dt || !dt->table_of_env)) return JSS_E_SHAPE;
-    if (*mode == 2 && (!dt || !dt->ops || !dt->rem || !dt->inst)) return JSS_E_SHAPE;
-    if (*mode == 2 && !sd->rem) return JSS_E_NULL;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -651,39 +555,26 @@ int jss_profiling_stamps(void *device_buffer) {      // [B][16] uint64 (NULL: of
 #endif
 
 const char *jss_error_string(int code) {
-    switch (code) {
-    case 0: return "ok";
-    case JSS_E_NULL: return "null pointer in JssDesc/JssState/JssOut or arguments";
-    case JSS_E_SHAPE: return "bad shape (batch/jmax/mmax/n_tables/n_sub)";
-    case JSS_E_KIND: return "unknown policy kind or kernel flavour";
-    case JSS_E_LDS: return "batch shape needs more LDS per workgroup than the device provides";
-    case JSS_E_RESIDENT: return "the batch does not fit the chip as one round of resident workgroups (step session)";
-    case JSS_E_SESSION: return "step session: bad step range (mailbox ring overrun, or the session was never opened)";
-    default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
-    }
+    const char *text = arg_error_string(code);
+    return text ? text : code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
 }
 
 int jss_reset(const JssDesc *desc, const JssState *state, const JssOut *out, const uint8_t *which, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
+    if (const int rc = check_reset(desc, state, out)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.which = which;
     return launch<kReset>(p, stream);
 }
 
 int jss_step(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_step(desc, state, actions, out)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.actions = actions;
     return launch<kStep>(p, stream);
 }
 
 int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_step(desc, state, actions, out)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.actions = actions; p.flags = JSS_ROLLOUT_AUTORESET;
     return launch<kStep>(p, stream);
@@ -693,9 +584,7 @@ int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t
 // env per wavefront at a time -- two_per_wave stays off)
 int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
                     const JssOut *out, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_logits(desc, lg))) return rc;
+    if (const int rc = check_step_logits(desc, state, lg, out)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.lg = *lg; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
     if (p.lg.row == 0) p.lg.row = desc->jmax + 1;
@@ -704,8 +593,7 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
 
 int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which, int32_t *hole, const JssOut *out,
                 void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
+    if (const int rc = check_reset(desc, state, out)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.which = which; p.hole = hole;
     return launch<kAdvance>(p, stream);
@@ -713,10 +601,7 @@ int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which
 
 int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t seed, uint32_t explore_q16,
                int32_t *actions, void *stream) {
-    int rc = check_args(desc, state, nullptr, false);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
-    if ((rc = check_kind(desc, kind, true))) return rc;
+    if (const int rc = check_policy(desc, state, kind, actions)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.actions_out = actions; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     return launch<kPolicy>(p, stream);
@@ -724,10 +609,7 @@ int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t se
 
 int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                 uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_kind(desc, kind))) return rc;
-    if (n_iter < 0) return JSS_E_SHAPE;
+    if (const int rc = check_rollout(desc, state, out, kind, n_iter)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = n_iter; p.flags = flags;
@@ -736,11 +618,7 @@ int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, i
 
 int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, int kind,
                    uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (!traj) return JSS_E_NULL;
-    if ((rc = check_kind(desc, kind))) return rc;
-    if (n_steps < 0) return JSS_E_SHAPE;
+    if (const int rc = check_trajectory(desc, state, out, traj, kind, n_steps)) return rc;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.t = *traj; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = n_steps; p.flags = flags;
@@ -749,11 +627,8 @@ int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out
 
 int jss_steps(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, const int32_t *actions,
               int32_t n_steps, void *stream) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if (n_steps < 0) return JSS_E_SHAPE;
-    if (n_steps == 0) return 0;                       // nothing to do (an empty action buffer has no address)
-    if (!actions) return JSS_E_NULL;
+    const int rc = check_steps(desc, state, out, actions, n_steps);
+    if (rc || n_steps == 0) return rc;                // (n_steps == 0: nothing to do)
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.actions = actions; p.n_iter = n_steps;
     if (traj) p.t = *traj;
@@ -762,12 +637,9 @@ int jss_steps(const JssDesc *desc, const JssState *state, const JssOut *out, con
 }
 
 int jss_session_open(const JssDesc *desc, const JssState *state, const JssOut *out, const JssSession *session, void *stream) {
-    int rc = check_args(desc, state, out, true);
+    int rc = check_session_open(desc, state, out, session);
     if (rc) return rc;
-    if (!session || !session->mail || !session->progress || !session->status) return JSS_E_NULL;
-    if (session->depth < 1 || session->timeout_ms < 0 || desc->batch < 1) return JSS_E_SHAPE;
     const int want = session->slots;
-    if (want != 0 && want != 1 && want != 2 && want != 4 && want != 8) return JSS_E_SHAPE;
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out;
     p.mail = reinterpret_cast<const unsigned long long *>(session->mail);
@@ -795,9 +667,7 @@ int jss_session_open(const JssDesc *desc, const JssState *state, const JssOut *o
 
 int jss_session_post(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t first_step,
                      int32_t n_steps, int32_t waited, void *stream) {
-    if (!desc || !session || !session->mail || !actions) return JSS_E_NULL;
-    if (first_step < 0 || n_steps < 1 || waited < 0 || waited > first_step || first_step + n_steps - waited > session->depth)
-        return JSS_E_SESSION;
+    if (const int rc = check_session_post(desc, session, actions, first_step, n_steps, waited)) return rc;
     hipLaunchKernelGGL(jss_session_post_kernel, dim3((desc->batch + kBlock - 1) / kBlock), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<unsigned long long *>(session->mail), actions,
                        desc->batch, session->depth, first_step, n_steps);
@@ -805,8 +675,7 @@ int jss_session_post(const JssDesc *desc, const JssSession *session, const int32
 }
 
 int jss_session_wait(const JssDesc *desc, const JssSession *session, int32_t steps_done, void *stream) {
-    if (!desc || !session || !session->progress || !session->status) return JSS_E_NULL;
-    if (steps_done < 0) return JSS_E_SESSION;
+    if (const int rc = check_session_wait(desc, session, steps_done)) return rc;
     SessionInfo info;
     {
         std::lock_guard<std::mutex> lock(g_sessions_mutex);
@@ -820,8 +689,7 @@ int jss_session_wait(const JssDesc *desc, const JssSession *session, int32_t ste
 }
 
 int jss_session_step(const JssDesc *desc, const JssSession *session, const int32_t *actions, int32_t step, void *stream) {
-    if (!desc || !session || !session->mail || !session->progress || !session->status || !actions) return JSS_E_NULL;
-    if (step < 0) return JSS_E_SESSION;
+    if (const int rc = check_session_step(desc, session, actions, step)) return rc;
     SessionInfo info;
     {
         std::lock_guard<std::mutex> lock(g_sessions_mutex);
@@ -836,8 +704,7 @@ int jss_session_step(const JssDesc *desc, const JssSession *session, const int32
 }
 
 int jss_session_close(const JssDesc *desc, const JssSession *session, int32_t next_step, void *stream) {
-    if (!desc || !session || !session->mail) return JSS_E_NULL;
-    if (next_step < 0) return JSS_E_SESSION;
+    if (const int rc = check_session_close(desc, session, next_step)) return rc;
     // (the caller has waited for every step it posted: the slot of next_step is free)
     {   // the session is over for the host: wait / step on it answer JSS_E_SESSION from here on (the progress / status buffers
         // may be freed by the caller once its stream has drained)
@@ -858,12 +725,8 @@ int jss_sync_check(void *stream) {
 
 int jss_rollout_steps(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                       uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub, void *const *streams) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_kind(desc, kind))) return rc;
-    if (n_steps < 0 || n_sub < 1 || n_sub > 16) return JSS_E_SHAPE;
-    if (!streams) return JSS_E_NULL;
-    if (n_steps == 0) return 0;                       // no step: nothing is launched, nothing is touched (both libraries)
+    int rc = check_rollout_steps(desc, state, out, kind, n_steps, n_sub, streams);
+    if (rc || n_steps == 0) return rc;                // (no step: nothing is launched, nothing is touched)
     Params p = {};
     p.d = *desc; p.s = *state; p.o = *out; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = 1; p.flags = flags & ~JSS_ROLLOUT_FORK_JOIN;
@@ -891,12 +754,8 @@ int jss_rollout_steps(const JssDesc *desc, const JssState *state, const JssOut *
 int jss_policy_step_steps(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                           uint32_t explore_q16, int32_t *actions, int32_t n_steps, int32_t flags, int32_t n_sub,
                           void *const *streams) {
-    int rc = check_args(desc, state, out, true);
-    if (rc) return rc;
-    if ((rc = check_kind(desc, kind, true))) return rc;
-    if (n_steps < 0 || n_sub < 1 || n_sub > 16) return JSS_E_SHAPE;
-    if (!streams || !actions) return JSS_E_NULL;
-    if (n_steps == 0) return 0;
+    int rc = check_policy_step_steps(desc, state, out, kind, actions, n_steps, n_sub, streams);
+    if (rc || n_steps == 0) return rc;
     Params pp = {}, ps = {};
     pp.d = *desc; pp.s = *state; pp.actions_out = actions; pp.kind = kind; pp.seed = seed; pp.explore_q16 = explore_q16;
     ps.d = *desc; ps.s = *state; ps.o = *out; ps.actions = actions; ps.flags = flags & JSS_ROLLOUT_AUTORESET;
@@ -930,8 +789,7 @@ int jss_policy_step_steps(const JssDesc *desc, const JssState *state, const JssO
 
 int jss_multi_reset(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                     const uint8_t *const *which, void *stream) {
-    int rc = check_multi(n_sets, descs, states, outs, true);
-    if (rc) return rc;
+    if (const int rc = check_multi_reset(n_sets, descs, states, outs)) return rc;
     Params ps[16];
     for (int i = 0; i < n_sets; ++i) {
         ps[i] = {};
@@ -942,12 +800,9 @@ int jss_multi_reset(int32_t n_sets, const JssDesc *const *descs, const JssState 
 
 int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const int32_t *const *actions,
                    const JssOut *const *outs, int32_t flags, void *stream) {
-    int rc = check_multi(n_sets, descs, states, outs, true);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_multi_step(n_sets, descs, states, actions, outs)) return rc;
     Params ps[16];
     for (int i = 0; i < n_sets; ++i) {
-        if (!actions[i]) return JSS_E_NULL;
         ps[i] = {};
         ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].actions = actions[i];
         ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
@@ -959,12 +814,9 @@ int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *
 // launch per set when the combination has no body in the grid
 int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
                           const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream) {
-    if (!lgs) return JSS_E_NULL;
-    int rc = check_multi(n_sets, descs, states, outs, true);
-    if (rc) return rc;
+    if (const int rc = check_multi_step_logits(n_sets, descs, states, lgs, outs)) return rc;
     Params ps[16];
     for (int i = 0; i < n_sets; ++i) {
-        if ((rc = check_logits(descs[i], lgs[i]))) return rc;
         ps[i] = {};
         ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].lg = *lgs[i]; ps[i].seed = seed;
         ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
@@ -975,13 +827,9 @@ int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const Jss
 
 int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, int kind, uint64_t seed,
                      uint32_t explore_q16, int32_t *const *actions, void *stream) {
-    int rc = check_multi(n_sets, descs, states, nullptr, false);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
+    if (const int rc = check_multi_policy(n_sets, descs, states, kind, actions)) return rc;
     Params ps[16];
     for (int i = 0; i < n_sets; ++i) {
-        if (!actions[i]) return JSS_E_NULL;
-        if ((rc = check_kind(descs[i], kind, true))) return rc;
         ps[i] = {};
         ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].actions_out = actions[i]; ps[i].kind = kind; ps[i].seed = seed;
         ps[i].explore_q16 = explore_q16;
@@ -992,13 +840,8 @@ int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState
 int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                       int kind, uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub,
                       void *const *streams) {
-    int rc = check_multi(n_sets, descs, states, outs, true);
-    if (rc) return rc;
-    if (n_steps < 0 || n_sub < 1 || n_sub > 16) return JSS_E_SHAPE;
-    if (!streams) return JSS_E_NULL;
-    for (int i = 0; i < n_sets; ++i)
-        if ((rc = check_kind(descs[i], kind))) return rc;
-    if (n_steps == 0) return 0;                       // no step: nothing is launched, nothing is touched (both libraries)
+    const int rc = check_multi_rollout(n_sets, descs, states, outs, kind, n_steps, n_sub, streams);
+    if (rc || n_steps == 0) return rc;                // (no step: nothing is launched, nothing is touched)
     Params ps[16];
     for (int i = 0; i < n_sets; ++i) {
         ps[i] = {};
@@ -1011,25 +854,20 @@ int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssStat
 int jss_rollout_steps_multi(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states,
                             const JssOut *const *outs, int kind, uint64_t seed, uint32_t explore_q16, int32_t n_steps,
                             int32_t flags, void *const *streams) {
-    if (!descs || !states || !outs || !streams) return JSS_E_NULL;
-    if (n_sets < 1 || n_sets > 16 || n_steps < 0) return JSS_E_SHAPE;
+    int rc = check_rollout_steps_multi(n_sets, descs, states, outs, kind, n_steps, streams);
+    if (rc) return rc;
     Params ps[16];
     LaunchPlan lps[16];
-    const bool nothing = n_steps == 0;                // (arguments are still checked)
     for (int i = 0; i < n_sets; ++i) {
-        int rc = check_args(descs[i], states[i], outs[i], true);
-        if (rc) return rc;
-        if ((rc = check_kind(descs[i], kind))) return rc;
         Params &p = ps[i];
         p = {};
         p.d = *descs[i]; p.s = *states[i]; p.o = *outs[i]; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
         p.n_iter = 1; p.flags = flags & ~JSS_ROLLOUT_FORK_JOIN;
         if ((rc = plan<kRollout1>(p, lps[i]))) return rc;
     }
-    if (nothing) return 0;
+    if (n_steps == 0) return 0;                       // (JSS_E_LDS is still reported)
     const bool fork_join = (flags & JSS_ROLLOUT_FORK_JOIN) != 0 && n_sets > 1;
     ForkJoinEvents *ev = nullptr;
-    int rc = 0;
     if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, n_sets)))) return rc;
     for (int s = 0; s < n_steps && !rc; ++s)
         for (int i = 0; i < n_sets && !rc; ++i) rc = fire(ps[i], lps[i], streams[i]);
@@ -1040,8 +878,7 @@ int jss_rollout_steps_multi(int32_t n_sets, const JssDesc *const *descs, const J
 // Taillard instances into the envs' own tables (jss_generate.hpp): sparse flags -> 64 envs' flags per wavefront, only the
 // flagged ones generated; no flags -> every env, kGenFullPerWave per wavefront
 int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, const uint8_t *which, void *stream) {
-    const int rc = check_generate(desc, state, gen);
-    if (rc) return rc;
+    if (const int rc = check_generate(desc, state, gen)) return rc;
     if (desc->batch == 0) return 0;
     GenParams g = {};
     g.ops = gen->ops; g.rem = gen->rem; g.inst = gen->inst;
@@ -1061,8 +898,7 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
 int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,
               const JssDesc *src_desc, const JssState *src, const JssOut *src_out, const int32_t *src_of_dst, void *stream) {
     int mode = 0;
-    const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode);
-    if (rc) return rc;
+    if (const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode)) return rc;
     if (dst_desc->batch == 0) return 0;
     const long long J = dst_desc->jmax, M = dst_desc->mmax, R = record_ints_of(*dst_desc);
     CloneParams p = {};
