@@ -72,6 +72,10 @@ SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "j
            "jss_multi_reset", "jss_multi_step", "jss_multi_policy", "jss_multi_rollout", "jss_step_logits",
            "jss_multi_step_logits", "jss_generate", "jss_clone")
 
+# include/jss_search.h: the companion header of the search calls (its own version; ABI_VERSION and SYMBOLS do not move)
+SEARCH_VERSION = 1
+SEARCH_SYMBOLS = ("jss_lookahead",)
+
 _p = C.c_void_p
 
 
@@ -114,6 +118,11 @@ class JssGen(C.Structure):
 
 class JssCloneDst(C.Structure):
     _fields_ = [("table_of_env", _p), ("ops", _p), ("rem", _p), ("inst", _p)]
+
+
+class JssLookahead(C.Structure):     # include/jss_search.h
+    _fields_ = [("n", C.c_int32), ("parent", _p), ("action", _p), ("id_base", C.c_int64), ("makespan", _p), ("steps", _p),
+                ("reward_num", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -174,6 +183,17 @@ def bind(lib):
     lib.jss_clone.restype, lib.jss_clone.argtypes = C.c_int, [D, S, O, C.POINTER(JssCloneDst), D, S, O, _p, _p]
     if lib.jss_abi_version() != ABI_VERSION:
         raise RuntimeError(f"library ABI {lib.jss_abi_version()} != expected {ABI_VERSION}")
+    return lib
+
+
+def bind_search(lib):
+    """Attach the prototypes of include/jss_search.h; raises AttributeError naming the first missing symbol."""
+    for name in SEARCH_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_lookahead.restype = C.c_int
+    lib.jss_lookahead.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssLookahead), C.c_int, C.c_uint64,
+                                  C.c_uint32, C.c_int32, _p]
     return lib
 
 

@@ -37,7 +37,7 @@ class HipBackend:
             raise ValueError(f"HipBackend needs a cuda device, got {self.device}")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.lib = _abi.bind(C.CDLL(path))
+        self.lib = _abi.bind_search(_abi.bind(C.CDLL(path)))
         if not self.lib.jss_backend().startswith(b"hip"):
             raise RuntimeError(f"{path} is not the HIP library ({self.lib.jss_backend()!r})")
         self._scalars = {}
@@ -226,7 +226,7 @@ class CpuBackend:
             if not os.path.isfile(path):
                 raise RuntimeError(f"device='cpu' needs {path}: build it with `g++ -O3 -std=c++17 -fopenmp -fPIC -shared "
                                    f"-Iinclude jssenv_amd/csrc/jss_cpu.cpp -o {path}` (automatic build failed: {exc})") from exc
-        self.lib = _abi.bind(C.CDLL(path))
+        self.lib = _abi.bind_search(_abi.bind(C.CDLL(path)))
         if not self.lib.jss_backend().startswith(b"cpu"):
             raise RuntimeError(f"{path} is not the CPU twin ({self.lib.jss_backend()!r})")
         self.threads = int(threads)

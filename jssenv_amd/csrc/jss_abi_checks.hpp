@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "jss_hip.h"
+#include "jss_search.h"
 
 namespace jss_abi {
 
@@ -276,6 +277,18 @@ inline int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout
     if (*mode == 2 && (!dt || !dt->ops || !dt->rem || !dt->inst)) return JSS_E_SHAPE;
     if (*mode == 2 && !sd->rem) return JSS_E_NULL;
     return 0;
+}
+
+// ---- search (include/jss_search.h) ---------------------------------------------------------------------------------
+// jss_lookahead: the batch as jss_rollout checks it, without a JssOut (nothing of the batch is written); the fused rollouts'
+// kinds (no JSS_POLICY_CR_F64)
+inline int check_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, int kind, int32_t n_iter) {
+    if (!d || !s || !la) return JSS_E_NULL;
+    int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
+    if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
+    return check_kind(d, kind);
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -41,6 +41,7 @@
 #include <cmath>   // logf / expf (jss_step_logits): the precise ones, on the device pass and on the emulator's host pass
 
 #include "jss_hip.h"
+#include "jss_search.h"
 
 namespace jss {
 
@@ -58,8 +59,10 @@ constexpr int kDurMask = 0xffff;
 //            registers until the session closes); only the session kernels are instantiated with it
 // kLogits = kStep with the action drawn in the kernel from the caller's logits (jss_step_logits: masked Gumbel-max,
 //           log-probability and entropy)
+// kLookahead = kRollout over CANDIDATES (jss_lookahead, include/jss_search.h): a group / wavefront per candidate loads its
+//           parent env, takes the forced first action and runs the rule to done in registers; only the score is written
 enum Mode { kReset = 0, kStep = 1, kAdvance = 2, kPolicy = 3, kRollout = 4, kRollout1 = 5, kTraj = 6, kSteps = 7, kSession = 8,
-            kLogits = 9 };
+            kLogits = 9, kLookahead = 10 };
 // where the op table lives: LDS (one instance shared by the batch) or global memory; kTabLdsC = LDS + compact 16-byte
 // job records (the three cached ops are re-read from the LDS table, the machine clocks rebuilt from the records)
 // kTabGlobalM = global memory + 24-byte medium records (packed kernels only: jobs, machines <= 32; the three cached ops in 21
@@ -102,6 +105,7 @@ struct Params {
     int32_t park_off_ints;            // LDS offset (ints) of the parked env sets: [wave][slot][kParkInt4][64 lanes] int4
     int32_t norm_slot_ints;           // packed kernel, kTabGlobal: ints between two slots' normaliser tables
     JssLogits lg;                     // kLogits (row resolved: >= jmax + 1)
+    JssLookahead la;                  // kLookahead: the candidates (the grid covers la.n, the batch is where the data comes from)
 #ifdef JSS_PROFILING
     unsigned long long *stamps;       // instrumented builds: [B][16] shader-clock stamps of the one-wavefront-per-env kernels (JSS_STAMP)
 #endif

@@ -1,7 +1,7 @@
 // jssenv_amd/csrc/jss_cpu.cpp -- libjss_cpu.so: the host-core twin of libjss_hip.so.
 //
-// Same C ABI (include/jss_hip.h: identical symbols, structs and memory layouts; every pointer is a host
-// pointer, `stream` is ignored, calls are synchronous), written from the kernels' queue-free restatement of
+// Same C ABI (include/jss_hip.h and its companion jss_search.h: identical symbols, structs and memory layouts; every
+// pointer is a host pointer, `stream` is ignored, calls are synchronous), written from the kernels' queue-free restatement of
 // the simulator: scalar C++ working in place on the 32-byte job records, OpenMP over envs.  It exists for
 // BASELINE config 1 ("runs without a GPU"), for `device="cpu"` users of the package, and as the multi-core
 // CPU baseline bench.py times next to the GPU (cpu_baseline kind "twin").  It shares no code with oracle/
@@ -765,6 +765,46 @@ int run(const Call &c, int mode) {
     return 0;
 }
 
+// jss_lookahead (include/jss_search.h): candidate k on a private copy of its parent -- header, full-layout job records,
+// machine clocks, a scratch solution block -- the forced action, then the rollout loop without auto-reset; the batch is only read
+void lookahead_one(const Call &c, const JssLookahead &la, int k) {
+    int makespan = -1, steps = 0;
+    long long reward_num = 0;
+    const int b = la.parent[k], a = la.action[k];
+    if (b >= 0 && b < c.d.batch) {
+        Env e = env_of(c, b, false);                                      // (compact / medium: already a thread-local copy)
+        static thread_local int32_t hdr[JSS_NH], job[JSS_MAX_JOBS * JSS_NF], tm[JSS_MAX_MACHINES], sol[JSS_MAX_JOBS * JSS_MAX_MACHINES];
+        std::memcpy(hdr, e.hdr, sizeof(hdr));
+        e.hdr = hdr;
+        if (!e.packed) {
+            std::memcpy(job, e.job, sizeof(int32_t) * e.jmax * JSS_NF);
+            std::memcpy(tm, e.tm, sizeof(int32_t) * e.mmax);
+            e.job = job;
+            e.tm = tm;
+        }
+        e.sol = sol;
+        const bool ok = e.J != 0 && n_legal(e) > 0 &&                    // never reset / done: nothing to evaluate
+                        (a == JSS_ACTION_SKIP || (a >= 0 && a < e.J && e.legal(a)) || (a == e.J && e.noop()));
+        if (ok) {
+            if (a != JSS_ACTION_SKIP) {
+                reward_num += step_env(e, a);
+                e.hdr[JSS_H_STEP] += 1;
+                steps = 1;
+            }
+            const uint64_t env_id = (uint64_t)(la.id_base + k);           // the fork's global id
+            for (int it = 0; it < c.n_iter && n_legal(e) > 0; ++it) {
+                reward_num += step_env(e, select_action(e, c, env_id));
+                e.hdr[JSS_H_STEP] += 1;
+                steps += 1;
+            }
+            if (n_legal(e) == 0) makespan = e.t();
+        }
+    }
+    la.makespan[k] = makespan;
+    if (la.steps) la.steps[k] = steps;
+    if (la.reward_num) la.reward_num[k] = reward_num;
+}
+
 // jss_generate (include/jss_hip.h): a Taillard instance into env b's own tables, the draws of the two Lehmer streams walked
 // in order -- the same double arithmetic as the host generator and the kernel, the same float32 reciprocals
 constexpr int64_t kLcgM = 2147483647;
@@ -1095,6 +1135,26 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
     }
 #else
     for (int b = 0; b < d.batch; ++b) one(b);
+#endif
+    return 0;
+}
+
+int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, int kind, uint64_t seed,
+                  uint32_t explore_q16, int32_t n_iter, void *) {
+    if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter;
+    const JssLookahead l = *la;
+#ifdef _OPENMP
+    if (c.d.threads > 0) {
+#pragma omp parallel for schedule(dynamic, 16) num_threads(c.d.threads)
+        for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
+    } else {
+#pragma omp parallel for schedule(dynamic, 16)
+        for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
+    }
+#else
+    for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
 #endif
     return 0;
 }

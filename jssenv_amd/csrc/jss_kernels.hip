@@ -6,6 +6,7 @@
 //   jss_packed_env.hpp  64/G envs per wavefront      (J, M <= G, G = 16 or 32)
 //   jss_generate.hpp    Taillard instances drawn into the envs' own tables (jss_generate)
 //   jss_clone.hpp       env k <- a copy of env src_of_dst[k], state, outputs and instance assignment (jss_clone)
+//   (jss_lookahead, include/jss_search.h: the kLookahead mode of the two env flavours above)
 //   jss_abi_checks.hpp  the C ABI's argument checks, shared with the host-core twin (jss_cpu.cpp)
 //
 // No MFMA anywhere: the path is integer indexing, there is no dense contraction.
@@ -155,14 +156,15 @@ int plan(Params &p, LaunchPlan &lp, bool by_class = false) {
     lp.two = false;
     if (G) {
         lp.envs_per_block = (kWave / G) * kWavesPerBlock;
-        p.obs_wave_floats = ((kWave / G) * (p.d.jmax < G ? p.d.jmax : G) * 7 + 3) & ~3;      // (jmax > G: a class inside padded rows)
+        p.obs_wave_floats = MODE == kLookahead ? 0                       // (kLookahead writes no observation)
+                          : ((kWave / G) * (p.d.jmax < G ? p.d.jmax : G) * 7 + 3) & ~3;      // (jmax > G: a class inside padded rows)
         p.mv_off_ints = p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats;
         p.norm_off_ints = p.mv_off_ints + kBlock;                       // one int per lane (six used per group), kTabGlobal
         lp.shmem = sizeof(int32_t) * ((size_t)p.norm_off_ints + (shared ? 0 : kBlock));
     } else {
         lp.two = !by_class && two_per_wave<MODE>(p.d, G, p.d.jmax);      // (the fused grid keeps one env per wavefront: its classes are parts of a batch)
         lp.envs_per_block = kWavesPerBlock * (lp.two ? 2 : 1);
-        p.obs_wave_floats = (p.d.jmax * 7 + 3 + 3) & ~3;               // + up to 3 floats of alignment shift (store_obs)
+        p.obs_wave_floats = MODE == kLookahead ? 0 : (p.d.jmax * 7 + 3 + 3) & ~3;   // + up to 3 floats of alignment shift (store_obs)
         if (p.obs_wave_floats < kWave) p.obs_wave_floats = kWave;      // unpack_env borrows it: one int per machine
         p.mv_off_ints = 0;
         p.norm_off_ints = 0;
@@ -936,6 +938,26 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
     const int per_block = kCloneBlock / kWave;
     const int blocks = (int)(((long long)dst_desc->batch + per_block - 1) / per_block);
     hipLaunchKernelGGL(jss_clone_kernel, dim3(blocks), dim3(kCloneBlock), 0, reinterpret_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+// Candidate moves scored by rule rollouts (include/jss_search.h): kLookahead, a group (packed) or a wavefront per candidate,
+// the kernel flavour and table layout of the batch as for jss_rollout.  The packed kernels address a parent's rows by a 32-bit
+// lane offset from the start of the batch's tensors; a batch too large for that runs on the one-wavefront-per-env kernels,
+// which address an env by a wave-uniform 64-bit base.
+int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, int kind, uint64_t seed,
+                  uint32_t explore_q16, int32_t n_iter, void *stream) {
+    if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
+    if (la->n == 0) return 0;
+    Params p = {};
+    p.d = *desc; p.s = *state; p.la = *la; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
+    // (the widest per-env rows a packed kernel offsets: job records, <= jmax x 32 bytes, and the 48-byte constants record)
+    if ((unsigned long long)desc->batch * ((unsigned long long)desc->jmax * JSS_NF * 4 + JSS_NC * 4) >= (1ull << 32))
+        p.d.kernel |= JSS_KERNEL_WAVE;
+    LaunchPlan lp;
+    if (const int rc = plan<kLookahead>(p, lp)) return rc;
+    const int blocks = (int)(((long long)la->n + lp.envs_per_block - 1) / lp.envs_per_block);
+    hipLaunchKernelGGL(lp.fn, dim3(blocks), dim3(kBlock), lp.shmem, reinterpret_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
 }
 

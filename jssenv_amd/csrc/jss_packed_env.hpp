@@ -428,8 +428,9 @@ __device__ __forceinline__ void p_check_no_op(PEnv<G> &e, const PCtx<G, TAB> &c,
 
 // ---------------------------------------------------------------------------------------
 // step(): jss_env.py:403-481.  `a` is group-uniform.  Returns the reward numerator.
+// SOL = false: the solution entry is not written (kLookahead: a candidate's env lives in registers only)
 // ---------------------------------------------------------------------------------------
-template <int G, int TAB, bool WT = false>
+template <int G, int TAB, bool WT = false, bool SOL = true>
 __device__ __forceinline__ int p_step(PEnv<G> &e, const PCtx<G, TAB> &c, const Params &p, int a, int32_t *mvtab) {
     const bool is_nope = c.alive && a == c.J;                            // :419
     const bool is_job = c.alive && a >= 0 && a < c.J;
@@ -446,7 +447,7 @@ __device__ __forceinline__ int p_step(PEnv<G> &e, const PCtx<G, TAB> &c, const P
         if (c.gl == m) e.tm = d;                                         // :446
         if (mine) {
             e.left = d;                                                  // :447
-            st_out<WT, int>(p.s.solution + (size_t)c.first_env * p.d.jmax * p.d.mmax,               // :454
+            if (SOL) st_out<WT, int>(p.s.solution + (size_t)c.first_env * p.d.jmax * p.d.mmax,               // :454
                             (((unsigned)c.rel * p.d.jmax + a) * p.d.mmax + e.todo) * 4u, e.t);
         }
         if (e.cur >= 0 && (e.cur >> 16) == m) {
@@ -1137,6 +1138,49 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
 }
 
 // ---------------------------------------------------------------------------------------
+// jss_lookahead (kLookahead, include/jss_search.h): candidate `cand` on my group.  The parent's state has just been unpacked
+// (c.alive: the parent exists and was reset); the forced first action a_in, if it is in the parent's mask, then kRollout's
+// loop without the auto-reset until done or n_iter policy steps.  Nothing but the score leaves the registers.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void p_lookahead_score(const Params &p, int cand, int makespan, int steps, int reward_num) {
+    p.la.makespan[cand] = makespan;
+    if (p.la.steps) p.la.steps[cand] = steps;
+    if (p.la.reward_num) p.la.reward_num[cand] = reward_num;
+}
+template <int G, int TAB>
+__device__ __forceinline__ void p_lookahead(PEnv<G> &e, PHeader &hd, const PCtx<G, TAB> &c, const Params &p, int cand,
+                                            bool cand_alive, int a_in, int32_t *mvtab) {
+    const bool a_job = grp_any<G>(c.gl == a_in && e.legal, c.gbase);   // job a_in is in the mask (collectives: every lane)
+    const bool live = grp_any<G>(e.legal, c.gbase);                      // not done (:639-653)
+    const bool ok = c.alive && live &&
+                    (a_in == JSS_ACTION_SKIP || (a_in >= 0 && a_in < c.J && a_job) || (a_in == c.J && e.noop != 0));
+    const int a0 = ok ? a_in : JSS_ACTION_SKIP;
+    const int rn0 = p_step<G, TAB, false, false>(e, c, p, a0, mvtab);
+    int n_steps = 0, sum_rn = 0;
+    if (a0 != JSS_ACTION_SKIP) {
+        hd.step += 1;
+        n_steps = 1;
+        sum_rn = rn0;
+    }
+    const uint64_t env_id = (uint64_t)(p.la.id_base + (int64_t)cand);   // the fork's global id
+    for (int it = 0; it < p.n_iter; ++it) {
+        const bool live_now = grp_any<G>(e.legal, c.gbase);              // (a collective: outside the && below)
+        const bool do_step = ok && live_now;
+        if (__ballot(do_step) == 0) break;                               // every candidate of the wave done
+        int a = p_select(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+        if (!do_step) a = JSS_ACTION_SKIP;
+        const int rn = p_step<G, TAB, false, false>(e, c, p, a, mvtab);
+        if (do_step) {
+            hd.step += 1;
+            n_steps += 1;
+            sum_rn += rn;
+        }
+    }
+    const bool done = !grp_any<G>(e.legal, c.gbase);
+    if (cand_alive && c.gl == 0) p_lookahead_score(p, cand, ok && done ? e.t : -1, ok ? n_steps : 0, ok ? sum_rn : 0);
+}
+
+// ---------------------------------------------------------------------------------------
 // the packed kernel, one env set (E = 64/G envs) per wave
 // ---------------------------------------------------------------------------------------
 // launch bounds: the largest occupancy each mode reaches without spilling (8 waves per SIMD = 64 VGPRs)
@@ -1177,11 +1221,26 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     c.gbase = lane & ~(G - 1);
     c.norm = lds + p.norm_off_ints + wave * kWave + c.gbase;             // kTabGlobal: my group's six normalisers
     c.first_env = block * EB + wave * E;                                 // wave-uniform
-    const bool wave_dead = c.first_env >= p.d.batch;                     // only in the last workgroup
+    // (kLookahead: the grid covers the candidates, `units`; once a group has read its candidate's parent, first_env = 0 and
+    //  rel = the parent's index address the parent's rows -- jss_lookahead keeps those offsets inside 32 bits)
+    const int units = MODE == kLookahead ? p.la.n : p.d.batch;
+    const bool wave_dead = c.first_env >= units;                         // only in the last workgroup
     const int e_in_wave = lane / G;
-    c.alive = c.first_env + e_in_wave < p.d.batch;
-    c.rel = (unsigned)(c.alive ? e_in_wave : (wave_dead ? 0 : p.d.batch - 1 - c.first_env));
-    const bool wave_whole = c.first_env + E <= p.d.batch;
+    c.alive = c.first_env + e_in_wave < units;
+    c.rel = (unsigned)(c.alive ? e_in_wave : (wave_dead ? 0 : units - 1 - c.first_env));
+    const bool wave_whole = c.first_env + E <= units;
+    int cand = 0, a_la = JSS_ACTION_SKIP;                                // kLookahead: my candidate and its forced action
+    const bool cand_alive = c.alive;
+    const bool no_env = MODE == kLookahead && p.d.batch == 0;            // kLookahead on an empty batch: no parent to load
+    if constexpr (MODE == kLookahead) {
+        cand = c.first_env + (int)c.rel;
+        const int par = wave_dead ? -1 : ld_off<int>(p.la.parent, (unsigned)cand * 4u);   // the parent first: every load behind it
+        if (!wave_dead) a_la = ld_off<int>(p.la.action, (unsigned)cand * 4u);
+        const bool pvalid = par >= 0 && par < p.d.batch;
+        c.alive = c.alive && pvalid;
+        c.rel = (unsigned)(pvalid ? par : 0);
+        c.first_env = 0;
+    }
     const size_t fe = (size_t)c.first_env;
     // 1. state loads first: they depend on nothing but the env index.  With kTabGlobal the env's shape and op table
     //    index come from its constants record (JssState.env_const, written by reset) and its six observation
@@ -1193,7 +1252,7 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     int4 hx = make_int4(0, 0, 0, 0);
     PLogits lr = {0, 0};
     c.tid = 0;
-    if (!wave_dead) {
+    if (!wave_dead && !no_env) {
         raw = p_issue_loads<G, TAB>(c, p);
         if constexpr (MODE == kLogits) {
             lr = p_issue_logits<G, TAB>(c, p);
@@ -1220,6 +1279,10 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
         __syncthreads();
     }
     if (wave_dead) return;
+    if (no_env) {
+        if (cand_alive && c.gl == 0) p_lookahead_score(p, cand, -1, 0, 0);
+        return;
+    }
     if (tab_in_lds(TAB)) {                            // one instance for the whole batch: scalar loads, issued up here
         const int32_t *ir = p.d.inst;
         c.J = ir[JSS_I_JOBS];
@@ -1254,6 +1317,10 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     // an env that was never reset (episode counter 0: every reset bumps it) is left alone by the step-type calls, like
     // the one-wavefront-per-env kernel and the host twin do (J == 0 in its constants record): no stores, no counters
     if (MODE != kReset && hd.episode == 0) c.alive = false;
+    if constexpr (MODE == kLookahead) {
+        p_lookahead(e, hd, c, p, cand, cand_alive, a_la, mvtab);
+        return;
+    }
     if constexpr (MODE == kLogits) a_in = p_logits_pick(e, c, p, (uint32_t)hd.episode, (uint32_t)hd.step, a_in, lr);
     int a_sched;
     bool restarted;
@@ -1275,7 +1342,7 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
 
 template <int G, int MODE, int TAB>
 __global__ __launch_bounds__(kBlock, (MODE == kTraj || MODE == kSteps) ? (tab_global(TAB) && !tab_medium(TAB) ? JSS_PTRAJ_GLOBAL_MIN_BLOCKS : JSS_PTRAJ_LDS_MIN_BLOCKS)
-                                     : MODE == kRollout ? (tab_global(TAB) ? 4 : 5)
+                                     : (MODE == kRollout || MODE == kLookahead) ? (tab_global(TAB) ? 4 : 5)
                                      : (tab_medium(TAB) && MODE == kRollout1) ? JSS_PACKED_MEDIUM_MIN_BLOCKS
                                      : ((tab_global(TAB) && (MODE == kStep || MODE == kLogits || MODE == kRollout1)) ? JSS_PACKED_GLOBAL_MIN_BLOCKS : 8))
 void jss_packed_kernel(Params p_arg) {
@@ -1287,7 +1354,7 @@ void jss_packed_kernel(Params p_arg) {
     // drop from 100-107 to 93-95 VGPRs, i.e. from 4 to 5 wavefronts per SIMD: trajectory +8 %, jss_steps +3 %, the rollout +2 %
     // on 15x15 x 65 536) and the shared-table recorder (+3 %); the shared-table rollout / jss_steps stay by value (+1 % at
     // 65 536 envs, -2..-3 % at 4 096).
-    JSS_PARAMS_OF(p, p_arg, (MODE == kTraj || MODE == kSteps || MODE == kRollout) && (tab_global(TAB) || MODE == kTraj));
+    JSS_PARAMS_OF(p, p_arg, (MODE == kTraj || MODE == kSteps || MODE == kRollout || MODE == kLookahead) && (tab_global(TAB) || MODE == kTraj));
     packed_block<G, MODE, TAB>(p, (int)blockIdx.x, lds);
 }
 

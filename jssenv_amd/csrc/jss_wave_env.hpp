@@ -415,8 +415,9 @@ __device__ __forceinline__ void check_no_op(Env<JPL> &e, const Ctx &c) {
 // ---------------------------------------------------------------------------------------
 // step(): jss_env.py:403-481.  `a` is wave-uniform.  Returns the reward numerator
 // (reward * max_time_op, an exact integer: scheduled duration minus idle-machine time).
+// SOL = false: the solution entry is not written (kLookahead: a candidate's env lives in registers only)
 // ---------------------------------------------------------------------------------------
-template <int JPL, bool WT = false>
+template <int JPL, bool WT = false, bool SOL = true>
 __device__ __forceinline__ int step_env(Env<JPL> &e, const Ctx &c, const Params &p, int a) {
     if (a == JSS_ACTION_SKIP || a == JSS_ACTION_RESET) return 0;         // RESET is handled by the caller
     if (a < 0 || a > c.J) {
@@ -448,7 +449,7 @@ __device__ __forceinline__ int step_env(Env<JPL> &e, const Ctx &c, const Params 
 #pragma unroll
         for (int s = 0; s < JPL; ++s)
             if (s == sa && c.lane == la) e.left[s] = d;                  // :447
-        if (c.lane == 0) st_out<WT, int>(p.s.solution + ((size_t)c.b * p.d.jmax + a) * p.d.mmax + k, 0u, e.t);  // :454
+        if (SOL && c.lane == 0) st_out<WT, int>(p.s.solution + ((size_t)c.b * p.d.jmax + a) * p.d.mmax + k, 0u, e.t);  // :454
 #pragma unroll
         for (int s = 0; s < JPL; ++s) {
             const uint64_t same = __ballot(e.cur[s] >= 0 && (e.cur[s] >> 16) == m);   // padding lanes hold cur = -1
@@ -1128,10 +1129,11 @@ __device__ __forceinline__ void loads_landed(const RawEnv<JPL> &r) {
 // join and the second env starts with an s_waitcnt for the first env's stores after all.
 // (NEXT = false, one env per wavefront: `live` false returns on the spot -- the form, and the code, these kernels always had)
 // (lgr: kLogits only, the caller's logits as loaded by wave_issue_logits)
+// (cand: kLookahead only, the candidate this wavefront evaluates; c.b is its parent)
 template <int JPL, int MODE, int TAB, bool NEXT = false>
 __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const HeaderWords &h, RawEnv<JPL> raw, int a_in,
                                             const int32_t *lds, float *scratch, const RawEnv<JPL> *next = nullptr,
-                                            const WLogits<JPL> *lgr = nullptr) {
+                                            const WLogits<JPL> *lgr = nullptr, int cand = 0) {
     const int b = c.b, lane = c.lane;
     Header hd = {0, 0};
     Env<JPL> e = {};
@@ -1207,6 +1209,35 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
         if (__ballot(e.tm > 0) == 0) e.err |= JSS_ERR_NOPE_IDLE;        // reference: IndexError (:517)
         else hole = advance(e, c);
         if (lane == 0 && p.hole) p.hole[b] = hole;
+    } else if constexpr (MODE == kLookahead) {
+        // jss_lookahead (include/jss_search.h): the forced first action, if the parent's mask has it, then kRollout's loop
+        // without the auto-reset until done or n_iter policy steps; one lane writes the score, nothing else leaves the registers
+        const int sa = a_in >> 6;
+        uint64_t lg = e.legal[0];
+        if (JPL > 1 && sa) lg = e.legal[JPL - 1];
+        const bool ok = any_legal(e) && (a_in == JSS_ACTION_SKIP || (a_in >= 0 && a_in < c.J && ((lg >> (a_in & 63)) & 1)) ||
+                                         (a_in == c.J && e.noop != 0));
+        if (ok) {
+            if (a_in != JSS_ACTION_SKIP) {
+                sum_rn = step_env<JPL, false, false>(e, c, p, a_in);
+                hd.step += 1;
+                n_steps = 1;
+            }
+            const uint64_t env_id = (uint64_t)(p.la.id_base + (int64_t)cand);   // the fork's global id
+            for (int it = 0; it < p.n_iter; ++it) {
+                if (!any_legal(e)) break;                                // done (:639-653)
+                const int a = select_action(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+                sum_rn += step_env<JPL, false, false>(e, c, p, a);
+                hd.step += 1;
+                n_steps += 1;
+            }
+        }
+        if (lane == 0) {
+            p.la.makespan[cand] = ok && !any_legal(e) ? e.t : -1;
+            if (p.la.steps) p.la.steps[cand] = n_steps;
+            if (p.la.reward_num) p.la.reward_num[cand] = sum_rn;
+        }
+        return;
     } else if (MODE == kPolicy) {
         const int a = select_action<JPL, true>(e, c, p, (uint64_t)(p.d.env_ids ? p.d.env_ids[b] : p.d.env_id_base + b),
                                     (uint32_t)hd.episode, (uint32_t)hd.step);
@@ -1291,12 +1322,14 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
 
 template <int JPL, int MODE, int TAB>
 __device__ __forceinline__ void wave_main(const Params &p, Ctx &c, const HeaderWords &h, bool ragged, int a_in,
-                                          const int32_t *lds, float *scratch) {
+                                          const int32_t *lds, float *scratch, int cand = 0) {
     RawEnv<JPL> raw;
     if (MODE != kReset) raw = wave_issue<JPL, TAB>(p, c.b, c.lane, h, ragged);   // (a reset reads nothing)
     if constexpr (MODE == kLogits) {
         const WLogits<JPL> lr = wave_issue_logits<JPL>(p, c.b, c.lane);
         wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch, nullptr, &lr);
+    } else if constexpr (MODE == kLookahead) {
+        wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch, nullptr, nullptr, cand);
     } else {
         wave_finish<JPL, MODE, TAB>(p, c, h, raw, a_in, lds, scratch);
     }
@@ -1329,7 +1362,7 @@ __device__ __forceinline__ void wave_main(const Params &p, Ctx &c, const HeaderW
 // recorder in addition by one occupancy step, 6 -> 5, the two-jobs-per-lane one-step rollout on 24-byte records 7 -> 6)
 constexpr int wave_min_blocks(int jpl, int mode, int tab) {
     return mode == kTraj ? (jpl == 2 ? JSS_TRAJ2_MIN_BLOCKS : JSS_TRAJ1_MIN_BLOCKS)
-         : mode == kRollout ? (jpl == 2 ? 5 : 7)
+         : (mode == kRollout || mode == kLookahead) ? (jpl == 2 ? 5 : 7)
          : (mode == kStep || mode == kLogits) ? (jpl == 2 ? 5 : 8)
          : mode == kSteps ? (jpl == 2 ? 4 : 6)
          : mode == kRollout1 ? (jpl == 2 ? (tab_medium(tab) ? 6 : JSS_WAVE2_MIN_BLOCKS) : JSS_WAVE_MIN_BLOCKS)
@@ -1346,14 +1379,25 @@ __device__ __forceinline__ void wave_block(const Params &p, int block, int32_t *
     float *scratch = reinterpret_cast<float *>(lds + p.table_lds_ints) + wave * p.obs_wave_floats;
 
     const int b_raw = block * kWavesPerBlock + wave;                      // one env per wave
-    const bool alive = b_raw < p.d.batch;
-    const int b = alive ? b_raw : p.d.batch - 1;
+    bool alive = b_raw < p.d.batch;
+    int b = alive ? b_raw : p.d.batch - 1;
+    int a_in = JSS_ACTION_SKIP;
+    int cand = 0;                                                         // kLookahead: the grid covers the candidates
+    bool pvalid = true;
+    if constexpr (MODE == kLookahead) {
+        alive = b_raw < p.la.n;
+        cand = alive ? b_raw : p.la.n - 1;
+        const int par = __builtin_amdgcn_readfirstlane(p.la.parent[cand]);   // the parent first: every load behind it
+        a_in = __builtin_amdgcn_readfirstlane(p.la.action[cand]);
+        pvalid = par >= 0 && par < p.d.batch;
+        b = pvalid ? par : 0;
+    }
     Ctx c;
     c.b = b;
     c.lane = lane;
     JSS_STAMP(p, b, 0, lane);
-    const HeaderWords h = load_header(p, b);
-    int a_in = JSS_ACTION_SKIP;
+    HeaderWords h = {};
+    if (MODE != kLookahead || pvalid) h = load_header(p, b);
     if (MODE == kStep) {
         a_in = __builtin_amdgcn_readfirstlane(p.actions[b]);
         // jss_step_autoreset: an env that reported done on the previous call is reset instead of stepped
@@ -1369,6 +1413,16 @@ __device__ __forceinline__ void wave_block(const Params &p, int block, int32_t *
         __syncthreads();
     }
     if (!alive || !selected) return;
+    if constexpr (MODE == kLookahead) {
+        if (!pvalid || __builtin_amdgcn_readfirstlane(h.J) == 0) {       // no such parent, or never reset: nothing to evaluate
+            if (lane == 0) {
+                p.la.makespan[cand] = -1;
+                if (p.la.steps) p.la.steps[cand] = 0;
+                if (p.la.reward_num) p.la.reward_num[cand] = 0;
+            }
+            return;
+        }
+    }
     const bool ragged = p.d.jmin > 0 && p.d.jmin < p.d.jmax;
     if (MODE == kReset) {
         const int tid = tab_in_lds(TAB) ? 0 : __builtin_amdgcn_readfirstlane(p.d.table_of_env ? p.d.table_of_env[b] : b);
@@ -1391,9 +1445,9 @@ __device__ __forceinline__ void wave_block(const Params &p, int block, int32_t *
     } else {
         // (J == 64 stays on the full-width body: the NOPE flag of its mask row lives at index 64, slot 1's first lane)
         if (NARROW && JPL == 2 && ragged && MODE != kSteps && __builtin_amdgcn_readfirstlane(h.J) < kWave)
-            wave_main<1, MODE, TAB>(p, c, h, ragged, a_in, lds, scratch);
+            wave_main<1, MODE, TAB>(p, c, h, ragged, a_in, lds, scratch, cand);
         else
-            wave_main<JPL, MODE, TAB>(p, c, h, ragged, a_in, lds, scratch);
+            wave_main<JPL, MODE, TAB>(p, c, h, ragged, a_in, lds, scratch, cand);
     }
 }
 
@@ -1403,7 +1457,7 @@ __global__ __launch_bounds__(kBlock, wave_min_blocks(JPL, MODE, TAB)) void jss_k
     // by value where a launch is one step: measured faster than in place although it spills SGPRs; in place for the launches
     // that loop over steps with the state in registers (jss_common.hpp: trajectory mode +6.5 % / +10 % on config 4's share /
     // config 5, the 64-iteration rollout +6 % / +3 %, jss_steps +2.5 %: there the up-front loads would stay live for the whole loop)
-    JSS_PARAMS_OF(p, p_arg, MODE == kTraj || MODE == kRollout || MODE == kSteps);
+    JSS_PARAMS_OF(p, p_arg, MODE == kTraj || MODE == kRollout || MODE == kSteps || MODE == kLookahead);
     wave_block<JPL, MODE, TAB>(p, (int)blockIdx.x, lds);
 }
 

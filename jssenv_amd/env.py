@@ -599,6 +599,91 @@ class BatchedJssEnv:
             self._packed_stale = True
         self._is_reset = self._is_reset or src._is_reset
 
+    # -- search: candidate moves scored by rule rollouts (jss_lookahead, include/jss_search.h) ----------------------------
+    def lookahead(self, kind: Union[str, int] = "SPT", actions=None, parents=None, n_iter: Optional[int] = None,
+                  seed: Optional[int] = None, explore: float = 0.0, id_base: int = 0):
+        """Score candidate moves without cloning: candidate k starts from env ``parents[k]``, takes ``actions[k]`` (job, J =
+        NOPE, -1 = none) and then follows the rule ``kind`` to the end of the episode, on the device, in registers; the batch
+        is not touched.  Exactly what ``fork([parents[k]], env_id_base=id_base + k)``, ``step(actions[k])`` and
+        ``rollout(kind, n_iter, seed, explore=explore, autoreset=False)`` would give, bit for bit, random draws included.
+
+        Returns device arrays ``(makespan, steps, ret)``: the clock at done (int32; -1 when the parent is done, the action is
+        not in its mask or out of range, the parent index is out of range, or the episode has not ended after ``n_iter``
+        policy steps), the env steps taken (int32, the forced one included) and the return, the sum of the rewards as
+        ``reward_num / max_time_op`` of the parent (float32).  ``parents`` / ``actions``: host or device int sequences of
+        equal length -> shape ``(n,)``; both None: every action of every env, parent-major, built on the device -> shape
+        ``(B, jmax + 1)`` (illegal and padded columns -1).  ``n_iter=None``: ``3 * jmax * mmax``, enough to finish any
+        episode.  A batch dealt out by shape class is evaluated in one launch on the padded extents' kernel."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before lookahead()")
+        self._no_open_session("lookahead")
+        if (actions is None) != (parents is None):
+            raise ValueError("lookahead: give both parents and actions, or neither (every action of every env)")
+        be = self.backend
+        if be.lib.jss_lookahead.argtypes is None:              # a library bound by _abi.bind alone (test backends)
+            _abi.bind_search(be.lib)
+        t = getattr(be, "torch", None)
+        B, A = self.batch, self.jmax + 1
+        k = _abi.policy_code(kind)
+        n_iter = 3 * self.jmax * self.mmax if n_iter is None else int(n_iter)
+        with be.on_device():
+            if parents is None:
+                shape = (B, A)
+                if t is not None:
+                    par = t.arange(B, dtype=t.int32, device=be.device).repeat_interleave(A)
+                    act = t.arange(A, dtype=t.int32, device=be.device).repeat(B)
+                else:
+                    par = np.repeat(np.arange(B, dtype=np.int32), A)
+                    act = np.tile(np.arange(A, dtype=np.int32), B)
+            else:
+                par, act = be.as_device(parents, "int32"), be.as_device(actions, "int32")
+                if t is None:
+                    par, act = par.copy(), act.copy()          # (as_device keeps one array alive: the second would drop the first)
+                if par.ndim != 1 or tuple(par.shape) != tuple(act.shape):
+                    raise ValueError("lookahead: parents and actions must be 1-d and of equal length")
+                shape = (int(par.shape[0]),)
+            n = int(np.prod(shape))
+            makespan, steps, rnum = be.zeros((n,), "int32"), be.zeros((n,), "int32"), be.zeros((n,), "int64")
+            if n:
+                p = be.ptr
+                la = _abi.JssLookahead(n, p(par), p(act), int(id_base), p(makespan), p(steps), p(rnum))
+                rc = be.lib.jss_lookahead(C.byref(self._desc), C.byref(self._state), C.byref(la), k,
+                                          self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter,
+                                          be.stream())
+                _abi.check(be.lib, rc, "jss_lookahead")
+            # the return: reward numerators over the parent's max_time_op (0 where nothing was evaluated)
+            if t is not None:
+                mto = self.env_const[:, _abi.C_MAX_TIME_OP].to(t.float64)[par.long().clamp(0, max(B - 1, 0))] if B else \
+                    t.ones(n, dtype=t.float64, device=be.device)
+                ret = t.where(mto > 0, rnum.to(t.float64) / mto.clamp(min=1), t.zeros_like(mto)).to(t.float32)
+            else:
+                mto = np.asarray(self.env_const)[:, _abi.C_MAX_TIME_OP].astype(np.float64)[np.clip(par, 0, max(B - 1, 0))] if B \
+                    else np.ones(n)
+                ret = np.where(mto > 0, rnum / np.maximum(mto, 1), 0.0).astype(np.float32)
+        return makespan.reshape(shape), steps.reshape(shape), ret.reshape(shape)
+
+    def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False):
+        """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the
+        rule to the end), and each env takes the action with the lowest makespan -- ties to the lowest index, -1 scores
+        count as +inf.  An env none of whose actions can be scored (it is done) is left alone (``JSS_ACTION_SKIP``), or reset
+        with ``autoreset``.  Everything stays on the device.  Returns ``step``'s tuple; ``info["action"]`` holds the actions
+        taken, ``info["scores"]`` the (B, jmax + 1) makespans."""
+        be = self.backend
+        t = getattr(be, "torch", None)
+        scores, _, _ = self.lookahead(kind, seed=seed)
+        none = _abi.ACTION_RESET if autoreset else _abi.ACTION_SKIP
+        with be.on_device():
+            if t is not None:
+                free = scores < 0
+                best = t.where(free, t.full_like(scores, 0x7FFFFFFF), scores).argmin(dim=1)
+                action = t.where(free.all(dim=1), t.full_like(best, none), best).to(t.int32)
+            else:
+                free = scores < 0
+                best = np.where(free, 0x7FFFFFFF, scores).argmin(axis=1)
+                action = np.where(free.all(axis=1), none, best).astype(np.int32)
+        obs, reward, done, truncated, _ = self.step(action)
+        return obs, reward, done, truncated, {"action": action, "scores": scores}
+
     # -- raw ABI handles (bench.py launches through these) -------------------------------
     @property
     def lib(self):
