@@ -6,7 +6,7 @@
 // BASELINE config 1 ("runs without a GPU"), for `device="cpu"` users of the package, and as the multi-core
 // CPU baseline bench.py times next to the GPU (cpu_baseline kind "twin").  It shares no code with oracle/
 // (the literal restatement of the reference used as the checker) -- tests/ compares the two.  With libjss_hip.so it
-// shares exactly one file, jss_abi_checks.hpp: the argument checks every entry point starts with, so that the two
+// shares two files, jss_abi_checks.hpp: the argument checks every entry point starts with, so that the two
 // libraries answer a bad argument list with the same code and touch nothing (tests/test_abi_arguments.py).
 //
 // Reference semantics (JSSEnv/envs/jss_env.py, cited per function) in the queue-free form: the reference's
@@ -18,8 +18,12 @@
 #include <limits>
 #include <mutex>
 #include <unordered_map>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
 
 #include "jss_abi_checks.hpp"
+#include "jss_env_rows.hpp"
 
 namespace {
 using namespace jss_abi;
@@ -749,19 +753,26 @@ void run_env(const Call &c, int mode, int b) {
     store_compact(e);
 }
 
-int run(const Call &c, int mode) {
-    const int B = c.d.batch;
+// body(i) for i in [0, n) on `threads` OpenMP threads (JssDesc.threads; 0: the runtime's default), dealt out statically or
+// -- DYNAMIC, for bodies of very uneven length -- 16 at a time
+template <bool DYNAMIC = false, class Body>
+void parallel_for(int n, int threads, Body &&body) {
 #ifdef _OPENMP
-    if (c.d.threads > 0) {
-#pragma omp parallel for schedule(static) num_threads(c.d.threads)
-        for (int b = 0; b < B; ++b) run_env(c, mode, b);
+    if (threads <= 0) threads = omp_get_max_threads();
+    if (DYNAMIC) {
+#pragma omp parallel for schedule(dynamic, 16) num_threads(threads)
+        for (int i = 0; i < n; ++i) body(i);
     } else {
-#pragma omp parallel for schedule(static)
-        for (int b = 0; b < B; ++b) run_env(c, mode, b);
+#pragma omp parallel for schedule(static) num_threads(threads)
+        for (int i = 0; i < n; ++i) body(i);
     }
 #else
-    for (int b = 0; b < B; ++b) run_env(c, mode, b);
+    for (int i = 0; i < n; ++i) body(i);
 #endif
+}
+
+int run(const Call &c, int mode) {
+    parallel_for(c.d.batch, c.d.threads, [&](int b) { run_env(c, mode, b); });
     return 0;
 }
 
@@ -1125,17 +1136,7 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
     auto one = [&](int b) {
         if (all || (which && which[b]) || (g.actions && g.actions[b] == JSS_ACTION_RESET)) generate_env(d, state, g, b);
     };
-#ifdef _OPENMP
-    if (d.threads > 0) {
-#pragma omp parallel for schedule(static) num_threads(d.threads)
-        for (int b = 0; b < d.batch; ++b) one(b);
-    } else {
-#pragma omp parallel for schedule(static)
-        for (int b = 0; b < d.batch; ++b) one(b);
-    }
-#else
-    for (int b = 0; b < d.batch; ++b) one(b);
-#endif
+    parallel_for(d.batch, d.threads, one);
     return 0;
 }
 
@@ -1145,17 +1146,7 @@ int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead
     Call c;
     c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter;
     const JssLookahead l = *la;
-#ifdef _OPENMP
-    if (c.d.threads > 0) {
-#pragma omp parallel for schedule(dynamic, 16) num_threads(c.d.threads)
-        for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
-    } else {
-#pragma omp parallel for schedule(dynamic, 16)
-        for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
-    }
-#else
-    for (int k = 0; k < l.n; ++k) lookahead_one(c, l, k);
-#endif
+    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
     return 0;
 }
 
@@ -1164,7 +1155,10 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
     int mode = 0;
     if (const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode)) return rc;
     const JssDesc dd = *dst_desc, sd = *src_desc;
-    const size_t J = dd.jmax, M = dd.mmax, R = record_ints_of(dd);
+    const size_t J = dd.jmax, M = dd.mmax;
+    EnvRow to[kMaxEnvRows], from[kMaxEnvRows];       // (one shape, check_clone: the same rows on both sides)
+    const int n_rows = cloned_rows(dd, *dst, *dst_out, to);
+    cloned_rows(sd, *src, *src_out, from);
     auto row = [](void *d, const void *s, size_t bytes, size_t k, size_t i) {
         std::memcpy(static_cast<char *>(d) + k * bytes, static_cast<const char *>(s) + i * bytes, bytes);
     };
@@ -1175,16 +1169,7 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
             dst->env[(size_t)k * JSS_NH + JSS_H_STATUS] |= JSS_ERR_BAD_INDEX;
             return;
         }
-        row(dst->env, src->env, JSS_NH * 4, k, i);
-        row(dst->env_const, src->env_const, JSS_NC * 4, k, i);
-        row(dst->job, src->job, J * R * 4, k, i);
-        if (R == JSS_NF) row(dst->machine, src->machine, M * 4, k, i);
-        row(dst->solution, src->solution, J * M * 4, k, i);
-        row(dst_out->real_obs, src_out->real_obs, J * 7 * 4, k, i);
-        row(dst_out->action_mask, src_out->action_mask, J + 1, k, i);
-        row(dst_out->reward, src_out->reward, 4, k, i);
-        row(dst_out->done, src_out->done, 1, k, i);
-        row(dst_out->makespan, src_out->makespan, 4, k, i);
+        for (int r = 0; r < n_rows; ++r) row(to[r].base, from[r].base, to[r].bytes, k, i);
         if (mode == 1) row(dst_tables->table_of_env, sd.table_of_env, 4, k, i);
         if (mode == 2) {
             row(dst_tables->ops, sd.ops, J * M * 4, k, i);
@@ -1193,17 +1178,7 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
             dst->env_const[(size_t)k * JSS_NC + JSS_C_TABLE] = k;   // env i's table is table k now
         }
     };
-#ifdef _OPENMP
-    if (dd.threads > 0) {
-#pragma omp parallel for schedule(static) num_threads(dd.threads)
-        for (int k = 0; k < dd.batch; ++k) one(k);
-    } else {
-#pragma omp parallel for schedule(static)
-        for (int k = 0; k < dd.batch; ++k) one(k);
-    }
-#else
-    for (int k = 0; k < dd.batch; ++k) one(k);
-#endif
+    parallel_for(dd.batch, dd.threads, one);
     return 0;
 }
 

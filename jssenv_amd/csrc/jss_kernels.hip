@@ -8,6 +8,7 @@
 //   jss_clone.hpp       env k <- a copy of env src_of_dst[k], state, outputs and instance assignment (jss_clone)
 //   (jss_lookahead, include/jss_search.h: the kLookahead mode of the two env flavours above)
 //   jss_abi_checks.hpp  the C ABI's argument checks, shared with the host-core twin (jss_cpu.cpp)
+//   jss_env_rows.hpp    the per-env tensors of a batch and their row sizes, shared with the twin (sub_batch, jss_clone)
 //
 // No MFMA anywhere: the path is integer indexing, there is no dense contraction.
 #include <mutex>
@@ -19,6 +20,7 @@
 #include "jss_generate.hpp"
 #include "jss_clone.hpp"
 #include "jss_abi_checks.hpp"
+#include "jss_env_rows.hpp"
 
 namespace {
 using namespace jss;
@@ -146,28 +148,38 @@ struct LaunchPlan {
 
 constexpr size_t kMaxDynamicLds = 64 * 1024;   // available to a workgroup without raising the function attribute
 
+// The head of the LDS layout, which the plain launches (plan) and the step session (plan_session) share: the staged table
+// of a shared-table batch, one observation image per wavefront and, for the packed flavour (G lanes per env), the move
+// and normaliser areas behind them.  packed_obs_rows: job rows per env of the packed image -- the two plans size it
+// differently, see their calls; with_obs == false: the mode writes no observation.
+void lds_layout(Params &p, int G, int packed_obs_rows, bool with_obs) {
+    p.region_ints = p.d.jmax * p.d.mmax;
+    p.table_lds_ints = p.d.n_tables == 1 ? ((p.region_ints + 3) & ~3) : 0;
+    if (G) {
+        p.obs_wave_floats = with_obs ? ((kWave / G) * packed_obs_rows * 7 + 3) & ~3 : 0;
+        p.mv_off_ints = p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats;
+        p.norm_off_ints = p.mv_off_ints + kBlock;                       // one int per lane (six used per group), kTabGlobal
+    } else {
+        p.obs_wave_floats = with_obs ? (p.d.jmax * 7 + 3 + 3) & ~3 : 0;   // + up to 3 floats of alignment shift (store_obs)
+        if (p.obs_wave_floats < kWave) p.obs_wave_floats = kWave;      // unpack_env borrows it: one int per machine
+        p.mv_off_ints = p.norm_off_ints = 0;
+    }
+}
+
 // Fills the launch-derived fields of `p` (LDS layout) from the whole batch's description.
 template <int MODE>
 int plan(Params &p, LaunchPlan &lp, bool by_class = false) {
     const bool shared = p.d.n_tables == 1;
-    p.region_ints = p.d.jmax * p.d.mmax;
-    p.table_lds_ints = shared ? ((p.region_ints + 3) & ~3) : 0;
     const int G = packed_group(p.d, by_class);
+    // (kLookahead writes no observation; packed image: min(jmax, G) rows -- jmax > G is a class inside padded rows)
+    lds_layout(p, G, p.d.jmax < G ? p.d.jmax : G, MODE != kLookahead);
     lp.two = false;
     if (G) {
         lp.envs_per_block = (kWave / G) * kWavesPerBlock;
-        p.obs_wave_floats = MODE == kLookahead ? 0                       // (kLookahead writes no observation)
-                          : ((kWave / G) * (p.d.jmax < G ? p.d.jmax : G) * 7 + 3) & ~3;      // (jmax > G: a class inside padded rows)
-        p.mv_off_ints = p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats;
-        p.norm_off_ints = p.mv_off_ints + kBlock;                       // one int per lane (six used per group), kTabGlobal
         lp.shmem = sizeof(int32_t) * ((size_t)p.norm_off_ints + (shared ? 0 : kBlock));
     } else {
         lp.two = !by_class && two_per_wave<MODE>(p.d, G, p.d.jmax);      // (the fused grid keeps one env per wavefront: its classes are parts of a batch)
         lp.envs_per_block = kWavesPerBlock * (lp.two ? 2 : 1);
-        p.obs_wave_floats = MODE == kLookahead ? 0 : (p.d.jmax * 7 + 3 + 3) & ~3;   // + up to 3 floats of alignment shift (store_obs)
-        if (p.obs_wave_floats < kWave) p.obs_wave_floats = kWave;      // unpack_env borrows it: one int per machine
-        p.mv_off_ints = 0;
-        p.norm_off_ints = 0;
         lp.shmem = sizeof(int32_t) * ((size_t)p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats);
     }
 #ifdef JSS_PROFILING
@@ -211,24 +223,20 @@ constexpr long long kTicksPerMs = 100000;        // the wall clock of the device
 int plan_session(Params &p, LaunchPlan &lp, int slots, int *blocks_out, int *active_out) {
     const bool shared = p.d.n_tables == 1, compact = p.d.record_ints == JSS_NFC;
     const int G = packed_group(p.d);
+    // A session knows no shape classes: jobs per lane go by jmax alone where plan honours JssDesc.jclass (wave_jpl), and
+    // the packed observation image has jmax rows where plan's has min(jmax, G) -- the same for every batch a session takes
     const int jpl = p.d.jmax <= kWave ? 1 : 2;
-    p.region_ints = p.d.jmax * p.d.mmax;
-    p.table_lds_ints = shared ? ((p.region_ints + 3) & ~3) : 0;
+    lds_layout(p, G, p.d.jmax, true);
     p.slots = slots;
     int envs_per_wave, park4;                        // park4: int4 per parked env set of one wavefront
     if (G) {
         envs_per_wave = kWave / G;
-        p.obs_wave_floats = ((kWave / G) * p.d.jmax * 7 + 3) & ~3;
-        p.mv_off_ints = p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats;
-        p.norm_off_ints = p.mv_off_ints + kBlock;
         p.norm_slot_ints = shared ? 0 : kBlock;
         p.park_off_ints = p.norm_off_ints + (shared ? 0 : slots * kBlock);
         park4 = (compact ? 1 : p.d.record_ints == JSS_NFM ? 2 : 3) * kWave + 8;
     } else {
         envs_per_wave = 1;
-        p.obs_wave_floats = (p.d.jmax * 7 + 3 + 3) & ~3;
-        if (p.obs_wave_floats < kWave) p.obs_wave_floats = kWave;
-        p.mv_off_ints = p.norm_off_ints = p.norm_slot_ints = 0;
+        p.norm_slot_ints = 0;
         p.park_off_ints = p.table_lds_ints + kWavesPerBlock * p.obs_wave_floats;
         park4 = (compact ? jpl : 2 * jpl) * kWave + kWave / 4 + 1;   // (medium records: lo + hi rows like full ones)
     }
@@ -332,28 +340,68 @@ int launch(Params &p, void *stream) {
     return rc ? rc : fire(p, lp, stream);
 }
 
+Params params_of(const JssDesc *desc, const JssState *state, const JssOut *out) {     // out == NULL: the call writes none
+    Params p = {};
+    p.d = *desc;
+    p.s = *state;
+    if (out) p.o = *out;
+    return p;
+}
+
+// ps[i] = params_of(set i), then each(ps[i], i) for what the sets of a jss_multi_* call differ in
+template <class Each>
+void params_of_sets(Params *ps, int n, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
+                    Each &&each) {
+    for (int i = 0; i < n; ++i) {
+        ps[i] = params_of(descs[i], states[i], outs ? outs[i] : nullptr);
+        each(ps[i], i);
+    }
+}
+
 // The description of envs [start, start + count) of the batch `p` describes, for the step-type modes: every per-env
-// pointer moves; the instance tables stay (an env's header names its table by its index in the WHOLE batch's
-// tables, so n_tables keeps describing those).  Not a description a reset may be launched with.
+// pointer moves (jss_env_rows.hpp, and the three below that are no state or output rows); the instance tables stay (an
+// env's header names its table by its index in the WHOLE batch's tables, so n_tables keeps describing those).  Not a
+// description a reset may be launched with -- except the whole batch, sub_batch(p, 0, batch), which is `p` itself.
 Params sub_batch(const Params &p, int start, int count) {
     Params q = p;
-    const size_t s0 = (size_t)start, jm = (size_t)p.d.jmax, mm = (size_t)p.d.mmax;
+    const size_t s0 = (size_t)start;
     q.d.batch = count;
     if (p.d.table_of_env) q.d.table_of_env = p.d.table_of_env + s0;
     if (p.d.env_ids) q.d.env_ids = p.d.env_ids + s0;
     q.d.env_id_base = p.d.env_id_base + start;
-    q.s.env = p.s.env + s0 * JSS_NH;
-    q.s.env_const = p.s.env_const + s0 * JSS_NC;
-    q.s.job = p.s.job + s0 * jm * record_ints_of(p.d);
-    q.s.machine = p.s.machine ? p.s.machine + s0 * mm : nullptr;
-    q.s.solution = p.s.solution + s0 * jm * mm;
-    if (p.s.counters) q.s.counters = p.s.counters + s0 * 4;
-    q.o.real_obs = p.o.real_obs + s0 * jm * 7;
-    q.o.action_mask = p.o.action_mask + s0 * (jm + 1);
-    q.o.reward = p.o.reward + s0;
-    q.o.done = p.o.done + s0;
-    q.o.makespan = p.o.makespan + s0;
+    for_each_env_row(p.d, q.s, q.o, [s0](auto *&rows, size_t bytes, bool) {
+        if (rows) rows = reinterpret_cast<decltype(+rows)>(reinterpret_cast<char *>(rows) + s0 * bytes);
+    });
     return q;
+}
+
+// How a batch is cut into at most n_sub contiguous parts: boundaries at multiples of 64 envs (whole workgroups, 16-byte
+// aligned rows); a part that would start behind the batch is dropped, the last part is shorter.  Returns the number of parts.
+struct Part {
+    int start, count;
+};
+int cut(int batch, int n_sub, Part *parts) {
+    const int chunk = (((batch + n_sub - 1) / n_sub) + 63) & ~63;
+    int n = 0;
+    for (int start = 0; n < n_sub && start < batch; start += chunk) parts[n++] = Part{start, batch - start < chunk ? batch - start : chunk};
+    return n;
+}
+
+// A window of n_steps steps over n_parts parts, part i on streams[i]: step s of a part depends only on its own step
+// s - 1, so one part's drain overlaps another's fill.  launch_part(i, streams[i]) launches ONE step of part i and returns
+// its error.  fork_join (JSS_ROLLOUT_FORK_JOIN; only with more than one part): the side streams start behind streams[0]
+// and streams[0] continues behind them all -- every stream is joined even when a launch failed (join_streams), and the
+// launch error wins over the join error.
+template <class LaunchPart>
+int issue_window(int n_parts, void *const *streams, int n_steps, bool fork_join, LaunchPart &&launch_part) {
+    fork_join = fork_join && n_parts > 1;
+    ForkJoinEvents *ev = nullptr;
+    int rc = 0;
+    if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, n_parts)))) return rc;
+    for (int s = 0; s < n_steps && !rc; ++s)
+        for (int i = 0; i < n_parts && !rc; ++i) rc = launch_part(i, streams[i]);
+    const int jrc = fork_join ? join_streams(*ev, streams, n_parts) : 0;
+    return rc ? rc : jrc;
 }
 
 // ---- several independent env sets in ONE grid (jss_multi_*) ------------------------------------------------------
@@ -434,100 +482,80 @@ int multi_flavour(const JssDesc &d) {
 
 // `ps[0..n)`: fully filled Params of the sets (everything but the launch-derived LDS fields).  One fused launch per step when
 // every set has a body in the grid, otherwise one plain launch per set and step.  n_sub > 1: every set is cut into n_sub
-// contiguous parts (boundaries at multiples of 64 envs) and part i of ALL sets is one grid on streams[i] -- step s of a part
-// depends only on its own step s - 1, so one part's drain overlaps another's fill (what jss_rollout_steps does for one set).
-// Step-type modes only (sub_batch); fork_join as in jss_rollout_steps.
+// contiguous parts (cut) and part i of ALL sets is issued on streams[i] -- as one grid when fused, else one launch per set --
+// by issue_window (what jss_rollout_steps does for one set).  Step-type modes only (sub_batch; the reset / policy modes come
+// with n_sub == 1, whose one part is the whole set).
 template <int MODE>
 int launch_multi(Params *ps, int n, int n_steps, int n_sub, void *const *streams, bool fork_join) {
+    // No fused body for a combination with a shared-table set, medium records on the one-wavefront-per-env shapes or more
+    // than kMultiMaxSets sets: parts and streams are the same either way, so that a caller who asked for overlap gets it.
     bool fused = n >= 2 && n <= kMultiMaxSets;
     for (int i = 0; i < n && fused; ++i) fused = multi_flavour(ps[i].d) != kMfNone;
-    constexpr int kMaxParts = 4;
+    constexpr int kMaxParts = 4;                                         // (16 in the single-set calls)
     if (n_sub > kMaxParts) n_sub = kMaxParts;
-    if (!fused) {
-        // No fused body for this combination (a shared-table set, medium records on the one-wavefront-per-env shapes, more
-        // than kMultiMaxSets sets): one plain launch per set, part and step -- parts and streams exactly as in the fused form
-        // (part i of every set on streams[i], JSS_ROLLOUT_FORK_JOIN honoured), so that a caller who asked for overlap gets it.
-        // (The reset / policy modes come here with n_sub == 1: sub_batch describes a part for the step-type modes only.)
-        struct Item { int set; Params p; };
-        static Item items[kMaxParts][16];                                 // (0.5 KB each: not on the stack of every caller)
-        static std::mutex items_mutex;
-        std::lock_guard<std::mutex> lock(items_mutex);
-        LaunchPlan lps[16];
-        int count[kMaxParts] = {}, parts = 0;
-        for (int i = 0; i < n; ++i) {
-            const int rc = plan<MODE>(ps[i], lps[i]);                    // (the plan of a set serves its parts: fire() sizes the grid)
-            if (rc) return rc;
-        }
-        for (int part = 0; part < n_sub; ++part) {
-            int k = 0;
-            for (int i = 0; i < n; ++i) {
-                const Params &whole = ps[i];
-                if (n_sub == 1) { items[parts][k++] = Item{i, whole}; continue; }
-                const int chunk = (((whole.d.batch + n_sub - 1) / n_sub) + 63) & ~63;
-                const int start = part * chunk;
-                if (start >= whole.d.batch) continue;
-                items[parts][k++] = Item{i, sub_batch(whole, start, whole.d.batch - start < chunk ? whole.d.batch - start : chunk)};
-            }
-            if (k) count[parts++] = k;
-        }
-        if (parts == 0) return 0;
-        ForkJoinEvents *ev = nullptr;
-        int rc = 0;
-        fork_join = fork_join && parts > 1;
-        if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, parts)))) return rc;
-        for (int s = 0; s < n_steps && !rc; ++s)
-            for (int part = 0; part < parts && !rc; ++part)
-                for (int k = 0; k < count[part] && !rc; ++k) rc = fire(items[part][k].p, lps[items[part][k].set], streams[part]);
-        const int jrc = fork_join ? join_streams(*ev, streams, parts) : 0;
-        return rc ? rc : jrc;
-    }
-    int order[kMultiMaxSets];
+    int order[16];
     for (int i = 0; i < n; ++i) order[i] = i;
-    for (int i = 1; i < n; ++i)                                          // insertion sort by flavour (= grid order), stable
+    for (int i = 1; fused && i < n; ++i)                                 // insertion sort by flavour (= grid order), stable
         for (int j = i; j > 0 && multi_flavour(ps[order[j]].d) < multi_flavour(ps[order[j - 1]].d); --j) {
             const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t;
         }
-    static MultiParams mp[kMaxParts];                                    // (2 KB each: not on the stack of every caller)
-    static std::mutex mp_mutex;
-    std::lock_guard<std::mutex> lock(mp_mutex);
-    size_t shmem = 0;
-    int blocks[kMaxParts] = {}, parts = 0;
+    // What the two forms plan differs, and stays so (which kernel a launch selects is measured behaviour): unfused, a set is
+    // planned WHOLE and its parts launch with that plan (fire() sizes the grid); fused, every part is planned for itself,
+    // class-aware, and every grid launches with the largest LDS size over ALL parts.
+    LaunchPlan whole[16];
+    for (int i = 0; i < n && !fused; ++i)
+        if (const int rc = plan<MODE>(ps[i], whole[i])) return rc;
+    struct Item { Params p; const LaunchPlan *lp; };
+    struct PartWork {                                                    // one part: the grid's argument, or its launches
+        MultiParams grid;
+        int blocks;
+        Item items[16];
+        int n_items;
+    };
+    static PartWork work[kMaxParts];                                     // (10 KB each: not on the stack of every caller)
+    static std::mutex work_mutex;
+    std::lock_guard<std::mutex> lock(work_mutex);
+    Part cuts[16][kMaxParts];
+    int n_cuts[16];
+    for (int i = 0; i < n; ++i) n_cuts[i] = cut(ps[i].d.batch, n_sub, cuts[i]);
+    size_t grid_lds = 0;
+    int parts = 0;
     for (int part = 0; part < n_sub; ++part) {
-        MultiParams &m = mp[parts];
+        PartWork &w = work[parts];
         int nb = 0, k = 0;
         for (int q = 0; q < n; ++q) {
-            Params &whole = ps[order[q]];
-            const int chunk = n_sub == 1 ? whole.d.batch : ((((whole.d.batch + n_sub - 1) / n_sub) + 63) & ~63);
-            const int start = part * chunk;
-            if (start >= whole.d.batch) continue;
-            LaunchPlan lp;
-            Params p = n_sub == 1 ? whole : sub_batch(whole, start, whole.d.batch - start < chunk ? whole.d.batch - start : chunk);
-            const int rc = plan<MODE>(p, lp, true);                      // (fills the LDS layout fields; class-aware; sized for THIS part)
-            if (rc) return rc;
-            nb += (p.d.batch + lp.envs_per_block - 1) / lp.envs_per_block;
-            m.p[k] = p;
-            m.block_end[k] = nb;
-            m.flavour[k] = multi_flavour(p.d);
-
-            if (lp.shmem > shmem) shmem = lp.shmem;
+            const int i = order[q];
+            if (part >= n_cuts[i]) continue;
+            Params p = sub_batch(ps[i], cuts[i][part].start, cuts[i][part].count);
+            if (fused) {
+                LaunchPlan lp;
+                if (const int rc = plan<MODE>(p, lp, true)) return rc;   // (fills the LDS layout fields; sized for THIS part)
+                nb += (p.d.batch + lp.envs_per_block - 1) / lp.envs_per_block;
+                w.grid.p[k] = p;
+                w.grid.block_end[k] = nb;
+                w.grid.flavour[k] = multi_flavour(p.d);
+                if (lp.shmem > grid_lds) grid_lds = lp.shmem;
+            } else {
+                w.items[k] = Item{p, &whole[i]};
+            }
             ++k;
         }
         if (k == 0) continue;
-        m.n_sets = k;
-        blocks[parts++] = nb;
+        w.grid.n_sets = w.n_items = k;
+        w.blocks = nb;
+        ++parts;
     }
     if (parts == 0) return 0;
-    ForkJoinEvents *ev = nullptr;
-    int rc = 0;
-    fork_join = fork_join && parts > 1;
-    if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, parts)))) return rc;
-    for (int s = 0; s < n_steps && !rc; ++s)                             // (the arguments are copied at every launch)
-        for (int i = 0; i < parts && !rc; ++i) {
-            hipLaunchKernelGGL(jss_multi_kernel<MODE>, dim3(blocks[i]), dim3(kBlock), shmem, reinterpret_cast<hipStream_t>(streams[i]), mp[i]);
+    return issue_window(parts, streams, n_steps, fork_join, [&](int part, void *stream) {
+        const PartWork &w = work[part];
+        int rc = 0;
+        if (fused) {                                                     // (the arguments are copied at every launch)
+            hipLaunchKernelGGL(jss_multi_kernel<MODE>, dim3(w.blocks), dim3(kBlock), grid_lds, reinterpret_cast<hipStream_t>(stream), w.grid);
             rc = (int)hipGetLastError();
         }
-    const int jrc = fork_join ? join_streams(*ev, streams, parts) : 0;
-    return rc ? rc : jrc;
+        for (int k = 0; !fused && k < w.n_items && !rc; ++k) rc = fire(w.items[k].p, *w.items[k].lp, stream);
+        return rc;
+    });
 }
 
 }  // namespace
@@ -563,22 +591,22 @@ const char *jss_error_string(int code) {
 
 int jss_reset(const JssDesc *desc, const JssState *state, const JssOut *out, const uint8_t *which, void *stream) {
     if (const int rc = check_reset(desc, state, out)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.which = which;
+    Params p = params_of(desc, state, out);
+    p.which = which;
     return launch<kReset>(p, stream);
 }
 
 int jss_step(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *stream) {
     if (const int rc = check_step(desc, state, actions, out)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.actions = actions;
+    Params p = params_of(desc, state, out);
+    p.actions = actions;
     return launch<kStep>(p, stream);
 }
 
 int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t *actions, const JssOut *out, void *stream) {
     if (const int rc = check_step(desc, state, actions, out)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.actions = actions; p.flags = JSS_ROLLOUT_AUTORESET;
+    Params p = params_of(desc, state, out);
+    p.actions = actions; p.flags = JSS_ROLLOUT_AUTORESET;
     return launch<kStep>(p, stream);
 }
 
@@ -587,8 +615,8 @@ int jss_step_autoreset(const JssDesc *desc, const JssState *state, const int32_t
 int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits *lg, uint64_t seed, int32_t flags,
                     const JssOut *out, void *stream) {
     if (const int rc = check_step_logits(desc, state, lg, out)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.lg = *lg; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
+    Params p = params_of(desc, state, out);
+    p.lg = *lg; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
     if (p.lg.row == 0) p.lg.row = desc->jmax + 1;
     return launch<kLogits>(p, stream);
 }
@@ -596,24 +624,24 @@ int jss_step_logits(const JssDesc *desc, const JssState *state, const JssLogits 
 int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which, int32_t *hole, const JssOut *out,
                 void *stream) {
     if (const int rc = check_reset(desc, state, out)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.which = which; p.hole = hole;
+    Params p = params_of(desc, state, out);
+    p.which = which; p.hole = hole;
     return launch<kAdvance>(p, stream);
 }
 
 int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t seed, uint32_t explore_q16,
                int32_t *actions, void *stream) {
     if (const int rc = check_policy(desc, state, kind, actions)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.actions_out = actions; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
+    Params p = params_of(desc, state, nullptr);
+    p.actions_out = actions; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     return launch<kPolicy>(p, stream);
 }
 
 int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                 uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
     if (const int rc = check_rollout(desc, state, out, kind, n_iter)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
+    Params p = params_of(desc, state, out);
+    p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = n_iter; p.flags = flags;
     return n_iter == 1 ? launch<kRollout1>(p, stream) : launch<kRollout>(p, stream);
 }
@@ -621,8 +649,8 @@ int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, i
 int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, int kind,
                    uint64_t seed, uint32_t explore_q16, int32_t n_steps, int32_t flags, void *stream) {
     if (const int rc = check_trajectory(desc, state, out, traj, kind, n_steps)) return rc;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.t = *traj; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
+    Params p = params_of(desc, state, out);
+    p.t = *traj; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = n_steps; p.flags = flags;
     return launch<kTraj>(p, stream);
 }
@@ -631,8 +659,8 @@ int jss_steps(const JssDesc *desc, const JssState *state, const JssOut *out, con
               int32_t n_steps, void *stream) {
     const int rc = check_steps(desc, state, out, actions, n_steps);
     if (rc || n_steps == 0) return rc;                // (n_steps == 0: nothing to do)
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.actions = actions; p.n_iter = n_steps;
+    Params p = params_of(desc, state, out);
+    p.actions = actions; p.n_iter = n_steps;
     if (traj) p.t = *traj;
     p.t.action = nullptr;
     return launch<kSteps>(p, stream);
@@ -642,8 +670,7 @@ int jss_session_open(const JssDesc *desc, const JssState *state, const JssOut *o
     int rc = check_session_open(desc, state, out, session);
     if (rc) return rc;
     const int want = session->slots;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out;
+    Params p = params_of(desc, state, out);
     p.mail = reinterpret_cast<const unsigned long long *>(session->mail);
     p.progress = session->progress;
     p.status = session->status;
@@ -729,28 +756,20 @@ int jss_rollout_steps(const JssDesc *desc, const JssState *state, const JssOut *
                       uint32_t explore_q16, int32_t n_steps, int32_t flags, int32_t n_sub, void *const *streams) {
     int rc = check_rollout_steps(desc, state, out, kind, n_steps, n_sub, streams);
     if (rc || n_steps == 0) return rc;                // (no step: nothing is launched, nothing is touched)
-    Params p = {};
-    p.d = *desc; p.s = *state; p.o = *out; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
+    Params p = params_of(desc, state, out);
+    p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
     p.n_iter = 1; p.flags = flags & ~JSS_ROLLOUT_FORK_JOIN;
     LaunchPlan lp;
     if ((rc = plan<kRollout1>(p, lp))) return rc;
-    // contiguous sub-batches with boundaries at multiples of 64 envs (whole workgroups, 16-byte aligned rows)
-    const int chunk = (((desc->batch + n_sub - 1) / n_sub) + 63) & ~63;
+    Part parts[16];
     Params sub[16];
-    int n = 0;
-    for (int i = 0; i < n_sub; ++i) {
-        const int start = i * chunk;
-        if (start >= desc->batch) break;
-        sub[n++] = sub_batch(p, start, desc->batch - start < chunk ? desc->batch - start : chunk);
-    }
-    if (n > 1 && (rc = plan<kRollout1>(sub[0], lp))) return rc;         // the kernel form goes by the size of a LAUNCH (two_per_wave)
-    const bool fork_join = (flags & JSS_ROLLOUT_FORK_JOIN) != 0 && n > 1;
-    ForkJoinEvents *ev = nullptr;
-    if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, n)))) return rc;
-    for (int s = 0; s < n_steps && !rc; ++s)
-        for (int i = 0; i < n && !rc; ++i) rc = fire(sub[i], lp, streams[i]);
-    const int jrc = fork_join ? join_streams(*ev, streams, n) : 0;
-    return rc ? rc : jrc;
+    const int n = cut(desc->batch, n_sub, parts);
+    for (int i = 0; i < n; ++i) sub[i] = sub_batch(p, parts[i].start, parts[i].count);
+    // the kernel form goes by the size of a LAUNCH (two_per_wave): with more than one part, by the first part's -- where
+    // jss_multi_rollout's per-set launches keep the whole set's plan (launch_multi)
+    if (n > 1 && (rc = plan<kRollout1>(sub[0], lp))) return rc;
+    return issue_window(n, streams, n_steps, (flags & JSS_ROLLOUT_FORK_JOIN) != 0,
+                        [&](int i, void *stream) { return fire(sub[i], lp, stream); });
 }
 
 int jss_policy_step_steps(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
@@ -758,45 +777,32 @@ int jss_policy_step_steps(const JssDesc *desc, const JssState *state, const JssO
                           void *const *streams) {
     int rc = check_policy_step_steps(desc, state, out, kind, actions, n_steps, n_sub, streams);
     if (rc || n_steps == 0) return rc;
-    Params pp = {}, ps = {};
-    pp.d = *desc; pp.s = *state; pp.actions_out = actions; pp.kind = kind; pp.seed = seed; pp.explore_q16 = explore_q16;
-    ps.d = *desc; ps.s = *state; ps.o = *out; ps.actions = actions; ps.flags = flags & JSS_ROLLOUT_AUTORESET;
+    Params pp = params_of(desc, state, nullptr), ps = params_of(desc, state, out);
+    pp.actions_out = actions; pp.kind = kind; pp.seed = seed; pp.explore_q16 = explore_q16;
+    ps.actions = actions; ps.flags = flags & JSS_ROLLOUT_AUTORESET;
     LaunchPlan lpp, lps;
     if ((rc = plan<kPolicy>(pp, lpp)) || (rc = plan<kStep>(ps, lps))) return rc;
-    const int chunk = (((desc->batch + n_sub - 1) / n_sub) + 63) & ~63;       // whole workgroups, 16-byte aligned rows
+    Part parts[16];
     Params subp[16], subs[16];
-    int n = 0;
-    for (int i = 0; i < n_sub; ++i) {
-        const int start = i * chunk;
-        if (start >= desc->batch) break;
-        const int count = desc->batch - start < chunk ? desc->batch - start : chunk;
-        subp[n] = sub_batch(pp, start, count);
-        subp[n].actions_out = actions + start;
-        subs[n] = sub_batch(ps, start, count);
-        subs[n].actions = actions + start;
-        ++n;
+    const int n = cut(desc->batch, n_sub, parts);
+    for (int i = 0; i < n; ++i) {
+        subp[i] = sub_batch(pp, parts[i].start, parts[i].count);
+        subp[i].actions_out = actions + parts[i].start;
+        subs[i] = sub_batch(ps, parts[i].start, parts[i].count);
+        subs[i].actions = actions + parts[i].start;
     }
-    if (n > 1 && (rc = plan<kStep>(subs[0], lps))) return rc;           // the kernel form goes by the size of a LAUNCH (two_per_wave)
-    const bool fork_join = (flags & JSS_ROLLOUT_FORK_JOIN) != 0 && n > 1;
-    ForkJoinEvents *ev = nullptr;
-    if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, n)))) return rc;
-    for (int s = 0; s < n_steps && !rc; ++s)
-        for (int i = 0; i < n && !rc; ++i) {
-            rc = fire(subp[i], lpp, streams[i]);
-            if (!rc) rc = fire(subs[i], lps, streams[i]);
-        }
-    const int jrc = fork_join ? join_streams(*ev, streams, n) : 0;
-    return rc ? rc : jrc;
+    if (n > 1 && (rc = plan<kStep>(subs[0], lps))) return rc;           // the kernel form goes by the size of a LAUNCH (two_per_wave), as in jss_rollout_steps
+    return issue_window(n, streams, n_steps, (flags & JSS_ROLLOUT_FORK_JOIN) != 0, [&](int i, void *stream) {
+        const int prc = fire(subp[i], lpp, stream);
+        return prc ? prc : fire(subs[i], lps, stream);
+    });
 }
 
 int jss_multi_reset(int32_t n_sets, const JssDesc *const *descs, const JssState *const *states, const JssOut *const *outs,
                     const uint8_t *const *which, void *stream) {
     if (const int rc = check_multi_reset(n_sets, descs, states, outs)) return rc;
     Params ps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        ps[i] = {};
-        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].which = which ? which[i] : nullptr;
-    }
+    params_of_sets(ps, n_sets, descs, states, outs, [&](Params &p, int i) { p.which = which ? which[i] : nullptr; });
     return launch_multi<kReset>(ps, n_sets, 1, 1, &stream, false);
 }
 
@@ -804,11 +810,10 @@ int jss_multi_step(int32_t n_sets, const JssDesc *const *descs, const JssState *
                    const JssOut *const *outs, int32_t flags, void *stream) {
     if (const int rc = check_multi_step(n_sets, descs, states, actions, outs)) return rc;
     Params ps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        ps[i] = {};
-        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].actions = actions[i];
-        ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
-    }
+    params_of_sets(ps, n_sets, descs, states, outs, [&](Params &p, int i) {
+        p.actions = actions[i];
+        p.flags = flags & JSS_ROLLOUT_AUTORESET;
+    });
     return launch_multi<kStep>(ps, n_sets, 1, 1, &stream, false);
 }
 
@@ -818,12 +823,10 @@ int jss_multi_step_logits(int32_t n_sets, const JssDesc *const *descs, const Jss
                           const JssLogits *const *lgs, uint64_t seed, int32_t flags, const JssOut *const *outs, void *stream) {
     if (const int rc = check_multi_step_logits(n_sets, descs, states, lgs, outs)) return rc;
     Params ps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        ps[i] = {};
-        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].lg = *lgs[i]; ps[i].seed = seed;
-        ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
-        if (ps[i].lg.row == 0) ps[i].lg.row = descs[i]->jmax + 1;
-    }
+    params_of_sets(ps, n_sets, descs, states, outs, [&](Params &p, int i) {
+        p.lg = *lgs[i]; p.seed = seed; p.flags = flags & JSS_ROLLOUT_AUTORESET;
+        if (p.lg.row == 0) p.lg.row = p.d.jmax + 1;
+    });
     return launch_multi<kLogits>(ps, n_sets, 1, 1, &stream, false);
 }
 
@@ -831,11 +834,9 @@ int jss_multi_policy(int32_t n_sets, const JssDesc *const *descs, const JssState
                      uint32_t explore_q16, int32_t *const *actions, void *stream) {
     if (const int rc = check_multi_policy(n_sets, descs, states, kind, actions)) return rc;
     Params ps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        ps[i] = {};
-        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].actions_out = actions[i]; ps[i].kind = kind; ps[i].seed = seed;
-        ps[i].explore_q16 = explore_q16;
-    }
+    params_of_sets(ps, n_sets, descs, states, nullptr, [&](Params &p, int i) {
+        p.actions_out = actions[i]; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
+    });
     return launch_multi<kPolicy>(ps, n_sets, 1, 1, &stream, false);
 }
 
@@ -845,11 +846,9 @@ int jss_multi_rollout(int32_t n_sets, const JssDesc *const *descs, const JssStat
     const int rc = check_multi_rollout(n_sets, descs, states, outs, kind, n_steps, n_sub, streams);
     if (rc || n_steps == 0) return rc;                // (no step: nothing is launched, nothing is touched)
     Params ps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        ps[i] = {};
-        ps[i].d = *descs[i]; ps[i].s = *states[i]; ps[i].o = *outs[i]; ps[i].kind = kind; ps[i].seed = seed;
-        ps[i].explore_q16 = explore_q16; ps[i].n_iter = 1; ps[i].flags = flags & JSS_ROLLOUT_AUTORESET;
-    }
+    params_of_sets(ps, n_sets, descs, states, outs, [&](Params &p, int) {
+        p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = 1; p.flags = flags & JSS_ROLLOUT_AUTORESET;
+    });
     return launch_multi<kRollout1>(ps, n_sets, n_steps, n_sub, streams, (flags & JSS_ROLLOUT_FORK_JOIN) != 0);
 }
 
@@ -860,21 +859,13 @@ int jss_rollout_steps_multi(int32_t n_sets, const JssDesc *const *descs, const J
     if (rc) return rc;
     Params ps[16];
     LaunchPlan lps[16];
-    for (int i = 0; i < n_sets; ++i) {
-        Params &p = ps[i];
-        p = {};
-        p.d = *descs[i]; p.s = *states[i]; p.o = *outs[i]; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
-        p.n_iter = 1; p.flags = flags & ~JSS_ROLLOUT_FORK_JOIN;
-        if ((rc = plan<kRollout1>(p, lps[i]))) return rc;
-    }
-    if (n_steps == 0) return 0;                       // (JSS_E_LDS is still reported)
-    const bool fork_join = (flags & JSS_ROLLOUT_FORK_JOIN) != 0 && n_sets > 1;
-    ForkJoinEvents *ev = nullptr;
-    if (fork_join && ((rc = events_for(streams[0], &ev)) || (rc = fork_streams(*ev, streams, n_sets)))) return rc;
-    for (int s = 0; s < n_steps && !rc; ++s)
-        for (int i = 0; i < n_sets && !rc; ++i) rc = fire(ps[i], lps[i], streams[i]);
-    const int jrc = fork_join ? join_streams(*ev, streams, n_sets) : 0;
-    return rc ? rc : jrc;
+    params_of_sets(ps, n_sets, descs, states, outs, [&](Params &p, int i) {
+        p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = 1; p.flags = flags & ~JSS_ROLLOUT_FORK_JOIN;
+        if (!rc) rc = plan<kRollout1>(p, lps[i]);
+    });
+    if (rc || n_steps == 0) return rc;                // (planned first: unlike the other windowed calls, JSS_E_LDS is still reported with no step)
+    return issue_window(n_sets, streams, n_steps, (flags & JSS_ROLLOUT_FORK_JOIN) != 0,
+                        [&](int i, void *stream) { return fire(ps[i], lps[i], stream); });
 }
 
 // Taillard instances into the envs' own tables (jss_generate.hpp): sparse flags -> 64 envs' flags per wavefront, only the
@@ -902,7 +893,7 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
     int mode = 0;
     if (const int rc = check_clone(dst_desc, dst, dst_out, dst_tables, src_desc, src, src_out, src_of_dst, &mode)) return rc;
     if (dst_desc->batch == 0) return 0;
-    const long long J = dst_desc->jmax, M = dst_desc->mmax, R = record_ints_of(*dst_desc);
+    const long long J = dst_desc->jmax, M = dst_desc->mmax;
     CloneParams p = {};
     // dwordx4 where both rows of every env are 16-byte aligned (row length and both bases), else dwords, else bytes
     auto add = [&](void *d, const void *s, long long bytes) {
@@ -914,16 +905,10 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
         g.unit = a % 16 == 0 ? 16 : a % 4 == 0 ? 4 : 1;
         g.n = (int32_t)(bytes / g.unit);
     };
-    add(dst->env, src->env, JSS_NH * 4);
-    add(dst->env_const, src->env_const, JSS_NC * 4);
-    add(dst->job, src->job, J * R * 4);
-    if (R == JSS_NF) add(dst->machine, src->machine, M * 4);
-    add(dst->solution, src->solution, J * M * 4);
-    add(dst_out->real_obs, src_out->real_obs, J * 7 * 4);
-    add(dst_out->action_mask, src_out->action_mask, J + 1);
-    add(dst_out->reward, src_out->reward, 4);
-    add(dst_out->done, src_out->done, 1);
-    add(dst_out->makespan, src_out->makespan, 4);
+    EnvRow to[kMaxEnvRows], from[kMaxEnvRows];       // (one shape, check_clone: the same rows on both sides)
+    const int n_rows = cloned_rows(*dst_desc, *dst, *dst_out, to);
+    cloned_rows(*src_desc, *src, *src_out, from);
+    for (int i = 0; i < n_rows; ++i) add(to[i].base, from[i].base, (long long)to[i].bytes);
     if (mode == 1) add(dst_tables->table_of_env, src_desc->table_of_env, 4);
     if (mode == 2) {
         add(dst_tables->ops, src_desc->ops, J * M * 4);
@@ -949,8 +934,8 @@ int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead
                   uint32_t explore_q16, int32_t n_iter, void *stream) {
     if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
     if (la->n == 0) return 0;
-    Params p = {};
-    p.d = *desc; p.s = *state; p.la = *la; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
+    Params p = params_of(desc, state, nullptr);
+    p.la = *la; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
     // (the widest per-env rows a packed kernel offsets: job records, <= jmax x 32 bytes, and the 48-byte constants record)
     if ((unsigned long long)desc->batch * ((unsigned long long)desc->jmax * JSS_NF * 4 + JSS_NC * 4) >= (1ull << 32))
         p.d.kernel |= JSS_KERNEL_WAVE;

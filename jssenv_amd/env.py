@@ -331,11 +331,25 @@ class BatchedJssEnv:
         the one place that says how the constructor (``order``), ``table_of_env`` or ``assign_instances`` dealt the envs."""
         return int(self.table_of_env_host[i])
 
+    @staticmethod
+    def _row_bytes(t, lead=1):
+        """Bytes of one env's row of ``t``: a per-env tensor (B, ...) -- a view of the arena ``_layout``, or ``solution`` -- or,
+        with ``lead=2``, a step-major (K, B, ...) record.  THE place that knows how large a row is: by the tensor's own
+        shape, which the arena ``specs`` gave it.  (A plain loop: this runs in every step of a batch dealt out by class.)"""
+        n = t.dtype.itemsize
+        for extent in t.shape[lead:]:
+            n *= extent
+        return n
+
+    def _row_ptr(self, t, a, lead=1):
+        """The address of env ``a``'s row of ``t``, or None for no tensor."""
+        return None if t is None else self.backend.ptr(t) + a * self._row_bytes(t, lead)
+
     def _build_class_views(self):
         """order='by_shape': one JssDesc / JssState / JssOut per shape class, each describing a contiguous range of THIS
         batch's padded tensors (every per-env pointer moved to the class's first env; the instance tables shared).  Rebuilt
         whenever something they copy changes: ``set_env_ids`` (the RNG keys), ``assign_instances`` (a class's jmin / extents)."""
-        be, B, J, M = self.backend, self.batch, self.jmax, self.mmax
+        be, J, M = self.backend, self.jmax, self.mmax
         cls_env = self._class_of_table[self.table_of_env_host]
         assert (np.diff(cls_env) >= 0).all()
         p = be.ptr
@@ -347,15 +361,14 @@ class BatchedJssEnv:
             a, b = int(idx[0]), int(idx[-1]) + 1
             assert b - a == idx.size
             jc, mc = int(self.jobs_per_env[a:b].max()), int(self.machines_per_env[a:b].max())
-            off = lambda t, per_env: p(t) + a * per_env * t.dtype.itemsize if t is not None else None     # noqa: E731
-            d = _abi.JssDesc(b - a, J, M, self.n_tables, p(self._ops), p(self._rem), p(self._inst), off(self._table_of_env, 1),
-                             off(self._env_ids, 1),      # explicit global env ids (set_env_ids) key the RNG of a class like the batch's
+            off = lambda t: self._row_ptr(t, a)     # noqa: E731
+            d = _abi.JssDesc(b - a, J, M, self.n_tables, p(self._ops), p(self._rem), p(self._inst), off(self._table_of_env),
+                             off(self._env_ids),         # explicit global env ids (set_env_ids) key the RNG of a class like the batch's
                              self.env_id_base + a, _abi.KERNEL[self.kernel], int(getattr(be, "threads", 0)),
                              int(self.jobs_per_env[a:b].min()), self.record_ints, float(self._desc.cr_factor), jc, mc)
-            st = _abi.JssState(off(self.env_header, _abi.NH), off(self.env_const, _abi.NC), off(self.job_state, J * self.record_ints),
-                               None if self.no_clocks else off(self.machine_state, M), off(self.solution, J * M), off(self.counters, 4))
-            o = _abi.JssOut(off(self.real_obs, J * 7), off(self.action_mask, J + 1), off(self.reward, 1), off(self.done, 1),
-                            off(self.makespan, 1))
+            st = _abi.JssState(off(self.env_header), off(self.env_const), off(self.job_state),
+                               None if self.no_clocks else off(self.machine_state), off(self.solution), off(self.counters))
+            o = _abi.JssOut(off(self.real_obs), off(self.action_mask), off(self.reward), off(self.done), off(self.makespan))
             descs.append(d), states.append(st), outs.append(o), spans.append((a, b, k))
         n = len(descs)
         D, S, O = C.POINTER(_abi.JssDesc), C.POINTER(_abi.JssState), C.POINTER(_abi.JssOut)
@@ -381,9 +394,8 @@ class BatchedJssEnv:
 
     def _class_ptrs(self, t):
         """(void* * n): where each class's rows of the (B, ...) tensor `t` start"""
-        be = self.backend
-        per_env = int(np.prod(t.shape[1:])) if len(t.shape) > 1 else 1
-        return (C.c_void_p * self._classes["n"])(*[be.ptr(t) + a * per_env * t.dtype.itemsize for a, _, _ in self._classes["spans"]])
+        base, row = self.backend.ptr(t), self._row_bytes(t)
+        return (C.c_void_p * self._classes["n"])(*[base + a * row for a, _, _ in self._classes["spans"]])
 
     def assign_instances(self, env_indices, table_indices):
         """Give envs ``env_indices`` the instances ``table_indices`` (indices into the ``instances`` this batch
@@ -885,10 +897,9 @@ class BatchedJssEnv:
     def _logits_struct(self, arg, temperature, logp, entropy, first=0):
         """JssLogits for the envs from `first` on: the logits (`_logits_arg`'s tuple) and the env's action / logp / entropy
         buffers, every pointer at env `first`'s row"""
-        be = self.backend
         ptr, row, dtype, _ = arg
-        item = 2 if dtype == _abi.LOGITS_BF16 else 4
-        at = lambda t, on: be.ptr(t) + first * 4 if on else None      # noqa: E731
+        item = 2 if dtype == _abi.LOGITS_BF16 else 4                  # (the caller's tensor, with the caller's row stride)
+        at = lambda t, on: self._row_ptr(t, first) if on else None      # noqa: E731
         return _abi.JssLogits(ptr + first * row * item, row, dtype, float(temperature), at(self._lg_action, True),
                               at(self._lg_logp, logp), at(self._lg_entropy, entropy))
 
@@ -1100,9 +1111,7 @@ class BatchedJssEnv:
 
     def _traj_at(self, bufs, a):
         """JssTraj over the step-major [K][B] buffers `bufs` for the range of the batch that starts at env `a`."""
-        be, J = self.backend, self.jmax
-        per_env = {"real_obs": J * 7 * 4, "action_mask": J + 1, "action": 4, "reward": 4, "done": 1}
-        ptr = lambda n: (be.ptr(bufs[n]) + a * per_env[n]) if bufs.get(n) is not None else None      # noqa: E731
+        ptr = lambda n: self._row_ptr(bufs.get(n), a, lead=2)      # noqa: E731
         return _abi.JssTraj(ptr("real_obs"), ptr("action_mask"), ptr("action"), ptr("reward"), ptr("done"), self.batch)
 
     def steps(self, actions, record=(), buffers: Optional[dict] = None):

@@ -18,6 +18,9 @@
 #ifndef JSS_EMU_HIP_RUNTIME_H
 #define JSS_EMU_HIP_RUNTIME_H
 
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <elf.h>
 #include <ucontext.h>
 
 #include <cassert>
@@ -27,6 +30,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
+#include <string>
 #include <vector>
 
 #define __global__
@@ -43,11 +48,75 @@ typedef void *hipStream_t;
 static inline hipError_t hipGetLastError() { return 0; }
 static inline hipError_t hipPeekAtLastError() { return 0; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
+
+/* ---- launch log (opt-in, like JSS_EMU_TRACE) ---------------------------------------------------------------------
+ * JSS_EMU_LAUNCH_LOG=<file>: the host side of the library appends one line per kernel launch (kernel instantiation by its
+ * demangled symbol, grid, block, dynamic LDS bytes, stream) and one per event record / stream wait.  Streams are opaque
+ * here, so a caller that passes small integers as its stream handles reads them back as "which of my streams"; events are
+ * numbered in the order they are created.  JSS_EMU_LAUNCH_DRY=1: a launch is logged and NOT executed -- full-size
+ * descriptors over buffers that do not exist cost nothing (tests/test_launch_log.py). */
+namespace emu {
+inline FILE *launch_log() {
+    static FILE *f = [] { const char *path = getenv("JSS_EMU_LAUNCH_LOG"); return path ? fopen(path, "a") : nullptr; }();
+    return f;
+}
+inline bool launch_dry() {
+    static const bool dry = getenv("JSS_EMU_LAUNCH_DRY") != nullptr;
+    return dry;
+}
+// The symbol of a kernel's address, from the library's own symbol table (the kernels in anonymous namespaces are local
+// symbols, which dladdr does not see): a name per instantiation, whatever the load address.
+inline const char *kernel_name(const void *fn) {
+    static std::map<uintptr_t, std::string> names;
+    static uintptr_t base = 0;
+    if (!base) {
+        Dl_info info;
+        if (!dladdr(fn, &info)) return "?";
+        base = (uintptr_t)info.dli_fbase;
+        std::vector<char> elf;
+        if (FILE *f = fopen(info.dli_fname, "rb")) {
+            fseek(f, 0, SEEK_END);
+            elf.resize((size_t)ftell(f));
+            fseek(f, 0, SEEK_SET);
+            if (fread(elf.data(), 1, elf.size(), f) != elf.size()) elf.clear();
+            fclose(f);
+        }
+        if (elf.size() < sizeof(Elf64_Ehdr)) return "?";
+        const Elf64_Ehdr *eh = (const Elf64_Ehdr *)elf.data();
+        const Elf64_Shdr *sh = (const Elf64_Shdr *)(elf.data() + eh->e_shoff);
+        for (int i = 0; i < eh->e_shnum; ++i) {
+            if (sh[i].sh_type != SHT_SYMTAB) continue;
+            const Elf64_Sym *sym = (const Elf64_Sym *)(elf.data() + sh[i].sh_offset);
+            const char *str = elf.data() + sh[sh[i].sh_link].sh_offset;
+            for (size_t k = 0; k < sh[i].sh_size / sizeof(Elf64_Sym); ++k) {
+                if (ELF64_ST_TYPE(sym[k].st_info) != STT_FUNC || !sym[k].st_value) continue;
+                int status = 0;
+                char *plain = abi::__cxa_demangle(str + sym[k].st_name, nullptr, nullptr, &status);
+                names[(uintptr_t)sym[k].st_value] = status == 0 ? plain : str + sym[k].st_name;
+                free(plain);
+            }
+        }
+    }
+    const auto it = names.find((uintptr_t)fn - base);
+    return it == names.end() ? "?" : it->second.c_str();
+}
+}  // namespace emu
+
 typedef void *hipEvent_t;
 #define hipEventDisableTiming 2
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (void *)1; return 0; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
+    static uintptr_t n_events = 0;
+    *e = (void *)++n_events;
+    return 0;
+}
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    if (FILE *f = emu::launch_log()) fprintf(f, "record event=%zu stream=%zu\n", (size_t)e, (size_t)s), fflush(f);
+    return 0;
+}
+static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    if (FILE *f = emu::launch_log()) fprintf(f, "wait stream=%zu event=%zu\n", (size_t)s, (size_t)e), fflush(f);
+    return 0;
+}
 static inline const char *hipGetErrorString(hipError_t) { return "emu"; }
 #define hipDeviceAttributeMultiprocessorCount 0
 static inline hipError_t hipGetDevice(int *d) { *d = 0; return 0; }
@@ -244,7 +313,11 @@ inline Block &the_block() {
 }  // namespace emu
 
 template <typename... KArgs, typename... Args>
-inline void hipLaunchKernelGGL(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
+inline void hipLaunchKernelGGL(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStream_t stream, Args... args) {
+    if (FILE *f = emu::launch_log())
+        fprintf(f, "launch %s grid=%u block=%u lds=%zu stream=%zu\n", emu::kernel_name((const void *)kernel), grid.x, block.x,
+                shmem, (size_t)stream), fflush(f);
+    if (emu::launch_dry()) return;
     emu::Block &b = emu::the_block();
     b.dyn_smem.assign(shmem + 64, (char)0x5A);   // LDS is not zeroed on hardware: poison it
     b.body = [=]() { kernel(args...); };
