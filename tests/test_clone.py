@@ -170,7 +170,8 @@ def test_clone_kernel_resources():
     """the clone kernel of the built library: no scratch, no spills, at most 64 VGPRs (8 wavefronts per SIMD)"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from kernel_resources import kernel_resources
-    rows = [r for r in kernel_resources(os.path.join(ROOT, "jssenv_amd", "libjss_hip.so")) if "jss_clone_kernel" in r[0]]
+    from jssenv_amd.build import build_extension
+    rows = [r for r in kernel_resources(build_extension()) if "jss_clone_kernel" in r[0]]      # (built here if build() has not run)
     assert len(rows) == 1
     _, vgpr, _, vspill, sspill, scratch = rows[0]
     assert scratch == 0 and vspill == 0 and sspill == 0 and vgpr <= 64
