@@ -76,6 +76,13 @@ SYMBOLS = ("jss_abi_version", "jss_error_string", "jss_backend", "jss_reset", "j
 SEARCH_VERSION = 1
 SEARCH_SYMBOLS = ("jss_lookahead",)
 
+# include/jss_rules.h: the companion header of the caller-weighted rules (its own version again).  The weighted selector has no
+# POLICY code: it is reached through these symbols only.
+RULES_VERSION = 1
+RULES_SYMBOLS = ("jss_rule_policy", "jss_rule_rollout", "jss_rule_lookahead")
+RW_DUR, RW_NEXT, RW_REM, RW_TOTAL, RW_OPS, RW_WAIT, RW_IDLE, RW_NOPE, RW_N = 0, 1, 2, 3, 4, 5, 6, 7, 8
+RW_NEVER_NOPE = -2**31
+
 _p = C.c_void_p
 
 
@@ -123,6 +130,10 @@ class JssCloneDst(C.Structure):
 class JssLookahead(C.Structure):     # include/jss_search.h
     _fields_ = [("n", C.c_int32), ("parent", _p), ("action", _p), ("id_base", C.c_int64), ("makespan", _p), ("steps", _p),
                 ("reward_num", _p)]
+
+
+class JssRule(C.Structure):          # include/jss_rules.h
+    _fields_ = [("weights", _p), ("stride", C.c_int32)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -194,6 +205,20 @@ def bind_search(lib):
     lib.jss_lookahead.restype = C.c_int
     lib.jss_lookahead.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssLookahead), C.c_int, C.c_uint64,
                                   C.c_uint32, C.c_int32, _p]
+    return lib
+
+
+def bind_rules(lib):
+    """Attach the prototypes of include/jss_rules.h; raises AttributeError naming the first missing symbol."""
+    for name in RULES_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    D, S, O, R = C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssOut), C.POINTER(JssRule)
+    lib.jss_rule_policy.restype, lib.jss_rule_policy.argtypes = C.c_int, [D, S, R, C.c_uint64, C.c_uint32, _p, _p]
+    lib.jss_rule_rollout.restype = C.c_int
+    lib.jss_rule_rollout.argtypes = [D, S, O, R, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _p]
+    lib.jss_rule_lookahead.restype = C.c_int
+    lib.jss_rule_lookahead.argtypes = [D, S, C.POINTER(JssLookahead), R, C.c_uint64, C.c_uint32, C.c_int32, _p]
     return lib
 
 

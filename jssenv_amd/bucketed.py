@@ -43,6 +43,12 @@ def shape_class(jobs: int, machines: int) -> int:
     return 2 if jobs <= 64 else 3
 
 
+def _stock_kind(kind):
+    if kind == "weighted":
+        raise NotImplementedError("BucketedJssEnv knows the stock rules only: weighted rules run on BatchedJssEnv (weights=)")
+    return kind
+
+
 class BucketedJssEnv:
     def __init__(self, instances: Sequence, batch: Optional[int] = None, device=None, seed: int = 0,
                  env_id_base: int = 0, launch: str = "grid", _backend=None):
@@ -142,7 +148,7 @@ class BucketedJssEnv:
             return
         self._check_reset("rollout_steps")
         be = self._backend
-        k = _abi.policy_code(kind)
+        k = _abi.policy_code(_stock_kind(kind))
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         q16 = int(round(explore * 65536))
         with be.on_device():
@@ -168,7 +174,7 @@ class BucketedJssEnv:
         self._check_reset("policy")
         be = self._backend
         with be.on_device():
-            rc = be.lib.jss_multi_policy(self._n_sets, self._sets[0], self._sets[1], _abi.policy_code(kind), self._seed(seed),
+            rc = be.lib.jss_multi_policy(self._n_sets, self._sets[0], self._sets[1], _abi.policy_code(_stock_kind(kind)), self._seed(seed),
                                          int(round(explore * 65536)), self._policy_out, be.stream())
         _abi.check(be.lib, rc, "jss_multi_policy")
         return {k: b._actions_out for k, b in self._each()}

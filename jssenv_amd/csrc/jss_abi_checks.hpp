@@ -11,6 +11,7 @@
 
 #include "jss_hip.h"
 #include "jss_search.h"
+#include "jss_rules.h"
 
 namespace jss_abi {
 
@@ -289,6 +290,37 @@ inline int check_lookahead(const JssDesc *d, const JssState *s, const JssLookahe
     if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
     if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
     return check_kind(d, kind);
+}
+
+// ---- caller-weighted rules (include/jss_rules.h) -------------------------------------------------------------------
+// a JssRule, where its call's namesake checks `kind`: the selector reads the remaining-work table whatever the weights are
+inline int check_rule(const JssDesc *d, const JssRule *rule) {
+    if (!rule || !rule->weights || !d->rem) return JSS_E_NULL;
+    if (reinterpret_cast<uintptr_t>(rule->weights) & 15) return JSS_E_SHAPE;      // rows are read four weights at a time
+    return rule->stride == 0 || rule->stride == JSS_RW_N ? 0 : JSS_E_SHAPE;
+}
+
+inline int check_rule_policy(const JssDesc *d, const JssState *s, const JssRule *rule, const int32_t *actions) {
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!actions) return JSS_E_NULL;
+    return check_rule(d, rule);
+}
+
+inline int check_rule_rollout(const JssDesc *d, const JssState *s, const JssOut *o, const JssRule *rule, int32_t n_iter) {
+    int rc = check_args(d, s, o, true);
+    if (rc) return rc;
+    if ((rc = check_rule(d, rule))) return rc;
+    return n_iter < 0 ? JSS_E_SHAPE : 0;
+}
+
+inline int check_rule_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, const JssRule *rule, int32_t n_iter) {
+    if (!d || !s || !la) return JSS_E_NULL;
+    int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
+    if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
+    return check_rule(d, rule);
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -42,6 +42,7 @@
 
 #include "jss_hip.h"
 #include "jss_search.h"
+#include "jss_rules.h"
 
 namespace jss {
 
@@ -106,6 +107,7 @@ struct Params {
     int32_t norm_slot_ints;           // packed kernel, kTabGlobal: ints between two slots' normaliser tables
     JssLogits lg;                     // kLogits (row resolved: >= jmax + 1)
     JssLookahead la;                  // kLookahead: the candidates (the grid covers la.n, the batch is where the data comes from)
+    JssRule rule;                     // kind == kKindWeighted (jss_rule_*, include/jss_rules.h): the caller's weight rows
 #ifdef JSS_PROFILING
     unsigned long long *stamps;       // instrumented builds: [B][16] shader-clock stamps of the one-wavefront-per-env kernels (JSS_STAMP)
 #endif
@@ -414,6 +416,71 @@ __device__ __forceinline__ CrKeyF cr_argmin_f64(CrKeyF k) {   // butterfly insid
     return k;
 }
 constexpr double kCrInf = __builtin_huge_val();
+
+// ---- caller-weighted rules (include/jss_rules.h) --------------------------------------------------------------------
+// Params.kind of the jss_rule_* calls: the launcher's own code, no JSS_POLICY_* constant (check_kind answers JSS_E_KIND for it).
+// The selector is compiled into the modes those calls launch and into no other (rule_mode: a template flag of p_select /
+// select_action, as F64 is): jss_rule_rollout plans kRollout for every n_iter, so the one-step kernels never carry it.
+constexpr int kKindWeighted = JSS_N_POLICIES;
+constexpr bool rule_mode(int mode) { return mode == kPolicy || mode == kRollout || mode == kLookahead; }
+// one term of a job's score: the product is exact in int64 (two int32 factors); the SUM wraps, so it is kept unsigned
+__device__ __forceinline__ unsigned long long rw_term(int w, int x) { return (unsigned long long)((long long)w * (long long)x); }
+// The arg-max of the signed 64-bit score runs on its two words, one after the other: the high words as signed, then the low
+// words as unsigned among the lanes that hold the high maximum.  A lane that takes no part carries the least key -- 0 in the
+// unsigned pass; INT32_MIN in the signed one, put together from a lane mask and a shift: as a literal it is no inline constant,
+// and the compiler keeps it in a register through the whole step loop, one these kernels do not have.  (A real key may equal
+// the least one: the lanes that take part are told apart by their own predicate.)
+__device__ __forceinline__ int rw_key_hi(int hi, bool part) {
+    const unsigned m = part ? ~0u : 0u;
+    return (int)(((unsigned)hi & m) | (~m << 31));
+}
+__device__ __forceinline__ int rw_hi(unsigned long long s) { return (int)(unsigned)(s >> 32); }
+__device__ __forceinline__ unsigned rw_lo(unsigned long long s) { return (unsigned)s; }
+__device__ __forceinline__ long long rw_score(int hi, unsigned lo) { return (long long)(((unsigned long long)(unsigned)hi << 32) | lo); }
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned row_umax(unsigned v) {
+    v = umax(v, (unsigned)JSS_DPP((int)v, 0xB1));
+    v = umax(v, (unsigned)JSS_DPP((int)v, 0x4E));
+    v = umax(v, (unsigned)JSS_DPP((int)v, 0x141));
+    v = umax(v, (unsigned)JSS_DPP((int)v, 0x140));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+    v = row_umax(v);
+    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
+    const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+    return umax(umax(a, b), umax(c, d));
+}
+// the instruction scheduler moves nothing across it (host pass and the test emulator: nothing)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JSS_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define JSS_SCHED_FENCE() do {} while (0)
+#endif
+// Where a packed kernel's weighted branch finds the JssRule: kRwArg = in the Params as the kernel reads them (the kernels that
+// read their arguments in place, and the one-launch policy kernel); kRwLds = in LDS.  The shared-table rollout / lookahead
+// kernels take their arguments by value (JSS_PARAMS_OF): there the rule's three dwords would sit in SGPRs through the whole step
+// loop of EVERY launch, the stock rules' included, and these kernels have none to spare (105 of 106: one more SGPR value parked
+// in a VGPR lane is the 73rd VGPR, a wavefront per SIMD less) -- nor two for the argument segment's address.  So the first
+// thread of the workgroup leaves them in four static LDS words in front of the barrier behind the op table's staging, and the
+// weighted branch reads them back into VGPRs, where it has room.
+enum RuleSource { kRwNo = 0, kRwArg = 1, kRwLds = 2 };
+constexpr int rule_source(int mode, int tab) {
+    return !rule_mode(mode) ? kRwNo : (mode != kPolicy && tab_in_lds(tab)) ? kRwLds : kRwArg;
+}
+constexpr int kRuleLdsBytes = 16;                 // static LDS of the kRwLds kernels, on top of a launch's dynamic LDS
+__device__ __forceinline__ int32_t *rule_stash() {
+    __shared__ int32_t stash[4];
+    return stash;
+}
+__device__ __forceinline__ void rule_stash_put(const JssRule &rule) {
+    int32_t *st = rule_stash();
+    const unsigned long long w = (unsigned long long)rule.weights;
+    st[0] = (int)(unsigned)w;
+    st[1] = (int)(unsigned)(w >> 32);
+    st[2] = rule.stride;
+}
+__device__ __forceinline__ bool rw_nope(int w_nope, long long best) { return w_nope != JSS_RW_NEVER_NOPE && (long long)w_nope > best; }
 
 constexpr uint64_t kExploreSeedXor = 0x5851F42D4C957F2DULL;
 constexpr uint64_t kLogitsSeedXor = JSS_LOGITS_SEED_XOR;   // K_LOGITS (include/jss_hip.h, jss_step_logits)

@@ -48,7 +48,9 @@ struct Call {   // one ABI call
     int n_iter = 0;
     int flags = 0;
     JssLogits lg = JssLogits();   // jss_step_logits (row resolved)
+    JssRule rule = JssRule();     // kind == kKindWeighted (jss_rule_*, include/jss_rules.h)
 };
+constexpr int kKindWeighted = JSS_N_POLICIES;   // Call.kind of the jss_rule_* calls: no public JSS_POLICY_* code
 
 // One env: pointers into the batch tensors + its instance.
 struct Env {
@@ -434,7 +436,30 @@ uint32_t rng_u32(uint64_t seed, uint64_t env_id, uint32_t episode, uint32_t step
     return fmix32(fmix32(a) ^ b);
 }
 
-int select_action(const Env &e, const Call &c, uint64_t env_id) {
+// include/jss_rules.h: the legal job with the largest score, the lowest index on ties; NOPE by its bias.  row = the env's
+// index in the call's batch.  The sum wraps: unsigned, read as signed.
+int select_weighted(const Env &e, const Call &c, int row) {
+    const int32_t *w = c.rule.weights + (size_t)row * c.rule.stride;
+    int best = -1;
+    long long best_score = 0;
+    for (int j = 0; j < e.J; ++j) {
+        if (!e.legal(j)) continue;
+        const int todo = e.todo(j);
+        const long long x[7] = {e.cur(j) & kDurMask, e.nxt(j) >= 0 ? e.nxt(j) & kDurMask : 0, e.rem[j * e.stride + todo],
+                                e.rem[j * e.stride], e.M - todo, e.w(j, JSS_F_IDLE_LAST), e.w(j, JSS_F_IDLE)};
+        uint64_t s = 0;
+        for (int f = 0; f < 7; ++f) s += (uint64_t)((long long)w[f] * x[f]);
+        if (best < 0 || (long long)s > best_score) {
+            best = j;
+            best_score = (long long)s;
+        }
+    }
+    if (e.noop() && w[JSS_RW_NOPE] != JSS_RW_NEVER_NOPE && (long long)w[JSS_RW_NOPE] > best_score) best = e.J;
+    return best;
+}
+
+// row: the env's index in the call's batch (the weighted rules' row)
+int select_action(const Env &e, const Call &c, uint64_t env_id, int row) {
     const uint32_t episode = (uint32_t)e.hdr[JSS_H_EPISODE], step = (uint32_t)e.hdr[JSS_H_STEP];
     const int nl = n_legal(e);
     const int n = nl + e.noop();
@@ -453,7 +478,8 @@ int select_action(const Env &e, const Call &c, uint64_t env_id) {
     int best_v = 0;
     const bool cr_f64 = kind == JSS_POLICY_CR && ((c.kind >> 24) & 1);    // JSS_POLICY_CR_F64: the reference's doubles themselves
     double best_ratio = 0.0;
-    for (int j = 0; j < e.J; ++j) {
+    if (kind == kKindWeighted) best = select_weighted(e, c, row);
+    for (int j = 0; j < e.J && kind != kKindWeighted; ++j) {
         if (!e.legal(j)) continue;
         const int todo = e.todo(j);
         if (cr_f64) {                                                     // dispatching.py:351-363, :391-399
@@ -696,7 +722,7 @@ void run_env(const Call &c, int mode, int b) {
         }
         break;
     case kPolicy:
-        c.actions_out[b] = select_action(e, c, env_id_of(c, b));
+        c.actions_out[b] = select_action(e, c, env_id_of(c, b), b);
         return;                                                           // no outputs rewritten
     default: {                                                            // n_iter x (policy + step), dispatching.py:55-75
         const uint64_t env_id = env_id_of(c, b);                          // kTraj: every iteration recorded (JssTraj)
@@ -725,7 +751,7 @@ void run_env(const Call &c, int mode, int b) {
                 e.hdr[JSS_H_STEP] = 0;
                 continue;
             }
-            const int a = select_action(e, c, env_id);
+            const int a = select_action(e, c, env_id, b);
             last_rn = step_env(e, a);
             e.hdr[JSS_H_STEP] += 1;
             n_steps += 1;
@@ -804,7 +830,7 @@ void lookahead_one(const Call &c, const JssLookahead &la, int k) {
             }
             const uint64_t env_id = (uint64_t)(la.id_base + k);           // the fork's global id
             for (int it = 0; it < c.n_iter && n_legal(e) > 0; ++it) {
-                reward_num += step_env(e, select_action(e, c, env_id));
+                reward_num += step_env(e, select_action(e, c, env_id, b));
                 e.hdr[JSS_H_STEP] += 1;
                 steps += 1;
             }
@@ -1145,6 +1171,36 @@ int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead
     if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter;
+    const JssLookahead l = *la;
+    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
+    return 0;
+}
+
+// include/jss_rules.h: the namesakes' calls with Call.kind = kKindWeighted and the weight rows
+int jss_rule_policy(const JssDesc *desc, const JssState *state, const JssRule *rule, uint64_t seed, uint32_t explore_q16,
+                    int32_t *actions, void *) {
+    if (const int rc = check_rule_policy(desc, state, rule, actions)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kKindWeighted; c.rule = *rule; c.seed = seed;
+    c.explore_q16 = explore_q16;
+    return run(c, kPolicy);
+}
+
+int jss_rule_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssRule *rule, uint64_t seed,
+                     uint32_t explore_q16, int32_t n_iter, int32_t flags, void *) {
+    if (const int rc = check_rule_rollout(desc, state, out, rule, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = *out; c.kind = kKindWeighted; c.rule = *rule; c.seed = seed; c.explore_q16 = explore_q16;
+    c.n_iter = n_iter; c.flags = flags;
+    return run(c, kRollout);
+}
+
+int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssRule *rule,
+                       uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *) {
+    if (const int rc = check_rule_lookahead(desc, state, la, rule, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kKindWeighted; c.rule = *rule; c.seed = seed; c.explore_q16 = explore_q16;
+    c.n_iter = n_iter;
     const JssLookahead l = *la;
     parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
     return 0;

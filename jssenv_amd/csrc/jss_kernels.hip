@@ -187,7 +187,9 @@ int plan(Params &p, LaunchPlan &lp, bool by_class = false) {
     p.stamps = g_stamps;
     lp.shmem += g_lds_pad;
 #endif
-    if (lp.shmem > kMaxDynamicLds) return JSS_E_LDS;
+    // (the shared-table packed rollout / lookahead kernels keep the rule of a jss_rule_* call in static LDS on top: rule_source)
+    const size_t static_lds = G && rule_source(MODE, shared ? kTabLds : kTabGlobal) == kRwLds ? kRuleLdsBytes : 0;
+    if (lp.shmem + static_lds > kMaxDynamicLds) return JSS_E_LDS;
     lp.fn = by_class ? nullptr : lp.two ? pick_two<MODE>(p.d.record_ints) : pick<MODE>(G, wave_jpl(p.d), shared, p.d.record_ints);   // (the grid has its own kernel)
     return 0;
 }
@@ -556,6 +558,18 @@ int launch_multi(Params *ps, int n, int n_steps, int n_sub, void *const *streams
         for (int k = 0; !fused && k < w.n_items && !rc; ++k) rc = fire(w.items[k].p, *w.items[k].lp, stream);
         return rc;
     });
+}
+
+// kLookahead over the candidates p.la of the batch p describes (jss_lookahead, jss_rule_lookahead)
+int launch_lookahead(Params &p, void *stream) {
+    // (the widest per-env rows a packed kernel offsets: job records, <= jmax x 32 bytes, and the 48-byte constants record)
+    if ((unsigned long long)p.d.batch * ((unsigned long long)p.d.jmax * JSS_NF * 4 + JSS_NC * 4) >= (1ull << 32))
+        p.d.kernel |= JSS_KERNEL_WAVE;
+    LaunchPlan lp;
+    if (const int rc = plan<kLookahead>(p, lp)) return rc;
+    const int blocks = (int)(((long long)p.la.n + lp.envs_per_block - 1) / lp.envs_per_block);
+    hipLaunchKernelGGL(lp.fn, dim3(blocks), dim3(kBlock), lp.shmem, reinterpret_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -936,14 +950,35 @@ int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead
     if (la->n == 0) return 0;
     Params p = params_of(desc, state, nullptr);
     p.la = *la; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
-    // (the widest per-env rows a packed kernel offsets: job records, <= jmax x 32 bytes, and the 48-byte constants record)
-    if ((unsigned long long)desc->batch * ((unsigned long long)desc->jmax * JSS_NF * 4 + JSS_NC * 4) >= (1ull << 32))
-        p.d.kernel |= JSS_KERNEL_WAVE;
-    LaunchPlan lp;
-    if (const int rc = plan<kLookahead>(p, lp)) return rc;
-    const int blocks = (int)(((long long)la->n + lp.envs_per_block - 1) / lp.envs_per_block);
-    hipLaunchKernelGGL(lp.fn, dim3(blocks), dim3(kBlock), lp.shmem, reinterpret_cast<hipStream_t>(stream), p);
-    return (int)hipGetLastError();
+    return launch_lookahead(p, stream);
+}
+
+// Caller-weighted rules (include/jss_rules.h): the namesakes' launches with Params.kind = kKindWeighted and the weight rows.
+// jss_rule_rollout plans kRollout whatever n_iter is: the one-step kernels (kRollout1) do not carry the weighted selector.
+int jss_rule_policy(const JssDesc *desc, const JssState *state, const JssRule *rule, uint64_t seed, uint32_t explore_q16,
+                    int32_t *actions, void *stream) {
+    if (const int rc = check_rule_policy(desc, state, rule, actions)) return rc;
+    Params p = params_of(desc, state, nullptr);
+    p.actions_out = actions; p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16;
+    return launch<kPolicy>(p, stream);
+}
+
+int jss_rule_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssRule *rule, uint64_t seed,
+                     uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
+    if (const int rc = check_rule_rollout(desc, state, out, rule, n_iter)) return rc;
+    Params p = params_of(desc, state, out);
+    p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16;
+    p.n_iter = n_iter; p.flags = flags;
+    return launch<kRollout>(p, stream);
+}
+
+int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssRule *rule,
+                       uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *stream) {
+    if (const int rc = check_rule_lookahead(desc, state, la, rule, n_iter)) return rc;
+    if (la->n == 0) return 0;
+    Params p = params_of(desc, state, nullptr);
+    p.la = *la; p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
+    return launch_lookahead(p, stream);
 }
 
 }  // extern "C"

@@ -113,6 +113,13 @@ __device__ __forceinline__ int grp_max(int v) {
 }
 
 template <int G>
+__device__ __forceinline__ unsigned grp_umax(unsigned v) {
+    v = row_umax(v);
+    if (G == 32) v = umax(v, (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F));
+    return v;
+}
+
+template <int G>
 __device__ __forceinline__ int grp_sum(int v) {
     v = row_sum(v);
     if (G == 32) v += __builtin_amdgcn_ds_swizzle(v, 0x401F);
@@ -474,7 +481,9 @@ __device__ __forceinline__ int p_step(PEnv<G> &e, const PCtx<G, TAB> &c, const P
 // action selectors (group-uniform result; -1 when nothing is legal)
 // ---------------------------------------------------------------------------------------
 // F64: the instantiation also carries JSS_POLICY_CR_F64's float64 selector (the policy kernels only)
-template <int G, int TAB, bool F64 = false>
+// RW: ... and the caller-weighted selector (include/jss_rules.h; rule_mode: kPolicy / kRollout / kLookahead), with the rule found
+// where rule_source says.  Every lane reads its env's row itself, in the branch: nothing of the rule is live outside it.
+template <int G, int TAB, bool F64 = false, int RW = kRwNo>
 __device__ __forceinline__ int p_select(const PEnv<G> &e, const PCtx<G, TAB> &c, const Params &p, uint64_t env_id,
                                         uint32_t episode, uint32_t step) {
     const int kind = p.kind & 0xFF;
@@ -497,6 +506,39 @@ __device__ __forceinline__ int p_select(const PEnv<G> &e, const PCtx<G, TAB> &c,
             key.idx = e.legal ? c.gl : kCrNone;
             key = cr_argmin_f64<G>(key);
             a = key.idx < kCrNone ? key.idx : c.J;                       // no job legal: NOPE
+        } else if (RW && kind == kKindWeighted) {
+            // Nothing of the rule is held across the step: my env's row is read in two halves of four weights (the second
+            // carries the NOPE bias), each used up before the next is asked for, its address formed anew in front of each.  The
+            // two fences keep the scheduler from asking for both halves at once; what that buys is register pressure, with this
+            // compiler -- tests/test_rules.py::test_rule_kernels_resources is what holds it.
+            auto row = [&]() -> const char * {
+                if (RW == kRwLds) {                                      // (a per-lane 64-bit address: no SGPR pair held)
+                    const int32_t *st = rule_stash();
+                    return reinterpret_cast<const char *>(((unsigned long long)(unsigned)st[1] << 32 | (unsigned)st[0]) +
+                                                          (unsigned long long)(((unsigned)c.first_env + c.rel) * (unsigned)st[2] * 4u));
+                }
+                return reinterpret_cast<const char *>(p.rule.weights + ((size_t)c.first_env + c.rel) * p.rule.stride);
+            };
+            const int4 wa = *reinterpret_cast<const int4 *>(row());
+            unsigned long long s = rw_term(wa.x, e.cur & kDurMask);
+            s += rw_term(wa.y, e.nxt >= 0 ? e.nxt & kDurMask : 0);
+            s += rw_term(wa.z, e.legal ? rem[e.todo] : 0);
+            s += rw_term(wa.w, e.legal ? rem[0] : 0);
+            JSS_SCHED_FENCE();
+            const int4 wb = *reinterpret_cast<const int4 *>(row() + 16);
+            s += rw_term(wb.x, c.M - e.todo);
+            s += rw_term(wb.y, e.idle_last);
+            s += rw_term(wb.z, e.idle);
+            JSS_SCHED_FENCE();
+            // arg-max (jss_common.hpp): high words, then low words among the lanes that hold the high maximum
+            const int sh = rw_hi(s);
+            const int hi = grp_max<G>(rw_key_hi(sh, e.legal));
+            const bool top = e.legal && sh == hi;
+            const unsigned sl = rw_lo(s);
+            const unsigned lo = grp_umax<G>(top ? sl : 0u);
+            const uint32_t hit = grp_ballot<G>(top && sl == lo, c.gbase);
+            a = hit ? __ffs(hit) - 1 : c.J;                              // ties: the lowest job index; no job legal: NOPE
+            if (hit && e.noop && rw_nope(wb.w, rw_score(hi, lo))) a = c.J;
         } else if (kind == JSS_POLICY_CR) {
             const int total = e.legal ? rem[0] : 0;                      // dispatching.py:373 job length
             const int remaining = e.legal ? rem[e.todo] : 1;             // :391
@@ -1071,7 +1113,7 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
     } else if (MODE == kPolicy) {
         const uint64_t env_id = (uint64_t)(p.d.env_ids ? ld_off<int64_t>(p.d.env_ids + fe, c.rel * 8u)
                                                        : p.d.env_id_base + (int64_t)(fe + c.rel));
-        const int a = p_select<G, TAB, true>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+        const int a = p_select<G, TAB, true, kRwArg>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
         if (c.alive && c.gl == 0) st_off<int>(p.actions_out + fe, c.rel * 4u, a);
     } else {  // kRollout / kRollout1 / kTraj
         const uint64_t env_id = (uint64_t)(p.d.env_ids ? ld_off<int64_t>(p.d.env_ids + fe, c.rel * 8u)
@@ -1095,7 +1137,7 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
                 hd.step = 0;
             }
             int a = JSS_ABLATED(p, JSS_ABLATE_SELECT) ? __ffs(grp_ballot<G>(e.legal, c.gbase)) - 1
-                                                      : p_select(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+                                                      : p_select<G, TAB, false, rule_source(MODE, TAB)>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
             if (!do_step) a = JSS_ACTION_SKIP;
             if (MODE == kRollout1) {
                 a_sched = a;
@@ -1167,7 +1209,7 @@ __device__ __forceinline__ void p_lookahead(PEnv<G> &e, PHeader &hd, const PCtx<
         const bool live_now = grp_any<G>(e.legal, c.gbase);              // (a collective: outside the && below)
         const bool do_step = ok && live_now;
         if (__ballot(do_step) == 0) break;                               // every candidate of the wave done
-        int a = p_select(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+        int a = p_select<G, TAB, false, rule_source(kLookahead, TAB)>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
         if (!do_step) a = JSS_ACTION_SKIP;
         const int rn = p_step<G, TAB, false, false>(e, c, p, a, mvtab);
         if (do_step) {
@@ -1211,6 +1253,9 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     constexpr int EB = E * kWavesPerBlock;            // envs per workgroup
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if constexpr (rule_source(MODE, TAB) == kRwLds) {                    // (first of all: no load is in flight yet; read behind the
+        if (threadIdx.x == 0) rule_stash_put(p.rule);                    //  barrier that follows the op table's staging)
+    }
     // obs image of this wave: E * jmax * 7 floats, 16-byte aligned (table_lds_ints is a multiple of 4)
     float *scratch = reinterpret_cast<float *>(lds + p.table_lds_ints) + wave * p.obs_wave_floats;
     int32_t *mvtab = lds + p.mv_off_ints + wave * kWave;                 // one int per lane, see p_check_no_op

@@ -478,7 +478,9 @@ __device__ __forceinline__ int nth_set_bit(uint64_t mask, int n, int lane) {
 }
 
 // F64: the instantiation also carries JSS_POLICY_CR_F64's float64 selector (the policy kernels only)
-template <int JPL, bool F64 = false>
+// RW: ... and the caller-weighted selector (include/jss_rules.h; rule_mode: kPolicy / kRollout / kLookahead).  The env's weight
+// row is wave-uniform: scalar loads at a wave-uniform address, the weights sit in SGPRs while the lanes form their scores.
+template <int JPL, bool F64 = false, bool RW = false>
 __device__ __forceinline__ int select_action(const Env<JPL> &e, const Ctx &c, const Params &p, uint64_t env_id,
                                              uint32_t episode, uint32_t step) {
     const int kind = p.kind & 0xFF;
@@ -507,7 +509,43 @@ __device__ __forceinline__ int select_action(const Env<JPL> &e, const Ctx &c, co
     int a = -1;
     // remaining-work table of my env: rem[j][k] = durations of ops k..M-1 of job j (MWR / LWR / CR)
     const int32_t *rem = p.d.rem + (size_t)c.tid * p.region_ints;
-    if (F64 && kind == JSS_POLICY_CR && ((p.kind >> 24) & 1)) {
+    if (RW && kind == kKindWeighted) {
+        const int32_t *w = p.rule.weights + (size_t)c.b * p.rule.stride;
+        // my lane's candidate: with two jobs per lane the better of the two slots first (the lower slot on ties: the lower index)
+        unsigned long long sc = 0;
+        bool part = false;
+        int slot = 0;
+#pragma unroll
+        for (int s = 0; s < JPL; ++s) {
+            const int j = s * kWave + c.lane;
+            const bool lg = (e.legal[s] >> c.lane) & 1;
+            unsigned long long v = rw_term(w[JSS_RW_DUR], e.cur[s] & kDurMask);
+            v += rw_term(w[JSS_RW_NEXT], e.nxt[s] >= 0 ? e.nxt[s] & kDurMask : 0);
+            v += rw_term(w[JSS_RW_REM], lg ? rem[j * c.stride + e.todo[s]] : 0);
+            v += rw_term(w[JSS_RW_TOTAL], lg ? rem[j * c.stride] : 0);
+            v += rw_term(w[JSS_RW_OPS], c.M - e.todo[s]);
+            v += rw_term(w[JSS_RW_WAIT], e.idle_last[s]);
+            v += rw_term(w[JSS_RW_IDLE], e.idle[s]);
+            if (lg && (!part || (long long)v > (long long)sc)) {
+                sc = v;
+                slot = s;
+                part = true;
+            }
+        }
+        // arg-max (jss_common.hpp): high words, then low words among the lanes that hold the high maximum
+        const int sh = rw_hi(sc);
+        const int hi = wave_max(rw_key_hi(sh, part));
+        const uint64_t top = __ballot(part && sh == hi);
+        const unsigned sl = rw_lo(sc);
+        const unsigned lo = wave_umax(((top >> c.lane) & 1) ? sl : 0u);
+        const bool hit = ((top >> c.lane) & 1) && sl == lo;
+#pragma unroll
+        for (int s = 0; s < JPL; ++s) {                                  // ties: the lowest job index
+            const uint64_t m = __ballot(hit && slot == s);
+            if (a < 0 && m) a = s * kWave + __ffsll((unsigned long long)m) - 1;
+        }
+        if (e.noop && rw_nope(w[JSS_RW_NOPE], rw_score(hi, lo))) a = c.J;
+    } else if (F64 && kind == JSS_POLICY_CR && ((p.kind >> 24) & 1)) {
         CrKeyF best;
         best.ratio = kCrInf;
         best.idx = kCrNone;
@@ -1226,7 +1264,7 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
             const uint64_t env_id = (uint64_t)(p.la.id_base + (int64_t)cand);   // the fork's global id
             for (int it = 0; it < p.n_iter; ++it) {
                 if (!any_legal(e)) break;                                // done (:639-653)
-                const int a = select_action(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+                const int a = select_action<JPL, false, true>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
                 sum_rn += step_env<JPL, false, false>(e, c, p, a);
                 hd.step += 1;
                 n_steps += 1;
@@ -1239,7 +1277,7 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
         }
         return;
     } else if (MODE == kPolicy) {
-        const int a = select_action<JPL, true>(e, c, p, (uint64_t)(p.d.env_ids ? p.d.env_ids[b] : p.d.env_id_base + b),
+        const int a = select_action<JPL, true, true>(e, c, p, (uint64_t)(p.d.env_ids ? p.d.env_ids[b] : p.d.env_id_base + b),
                                     (uint32_t)hd.episode, (uint32_t)hd.step);
         if (lane == 0) p.actions_out[b] = a;
         return;
@@ -1270,7 +1308,7 @@ __device__ __forceinline__ void wave_finish(const Params &p, Ctx &c, const Heade
                 restarted = true;
                 continue;
             }
-            const int a = select_action(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
+            const int a = select_action<JPL, false, MODE == kRollout>(e, c, p, env_id, (uint32_t)hd.episode, (uint32_t)hd.step);
             JSS_STAMP(p, b, 3, a);
             if (MODE == kRollout1) a_sched = a;
             last_rn = step_env(e, c, p, a);

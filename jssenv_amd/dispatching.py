@@ -227,6 +227,130 @@ class CriticalRatio(DispatchingRule):                                     # disp
         return job
 
 
+# ---- caller-weighted rules (include/jss_rules.h) ------------------------------------------------------------------
+# A rule is a row of 8 int32: weights of seven quantities of a legal job and a NOPE bias.
+RW_DUR, RW_NEXT, RW_REM, RW_TOTAL, RW_OPS, RW_WAIT, RW_IDLE, RW_NOPE = range(8)
+NEVER_NOPE = -2**31
+
+
+def _row(**w):
+    r = np.zeros(8, dtype=np.int32)
+    r[RW_NOPE] = NEVER_NOPE
+    for k, v in w.items():
+        r[{"dur": RW_DUR, "rem": RW_REM, "ops": RW_OPS, "wait": RW_WAIT}[k]] = v
+    return r
+
+
+# the six linear stock rules as weight rows: each plays exactly what its stock rule plays (CriticalRatio is a ratio, not a row)
+RULE_WEIGHTS = {"SPT": _row(dur=-1), "FIFO": _row(wait=1), "MWR": _row(rem=1), "LWR": _row(rem=-1), "MOR": _row(ops=1),
+                "LOR": _row(ops=-1)}
+
+
+def _wrap64(v: int) -> int:
+    """A Python int reduced mod 2^64 and read as signed: the device's wrapping 64-bit sum."""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
+class WeightedRule(DispatchingRule):
+    """A dispatching rule given by integer weights: among the legal jobs, the one with the largest
+    ``score(j) = sum_f weights[f] * x_f(j)`` -- x = (duration of the current op, duration of the next op or 0, remaining work,
+    job length, remaining ops, idle time since the last op, total idle time) -- in wrapping signed 64-bit arithmetic, the
+    lowest job index on ties; NOPE when only NOPE is legal, or when it is legal, ``weights[7]`` is not ``NEVER_NOPE`` and
+    ``weights[7]`` exceeds the best score.  Then, where NOPE is legal, NOPE with probability ``explore`` (default 0: a
+    weighted rule says itself when to wait).  Float weights are the caller's to quantise: scale, round.
+
+    ``__call__`` restates this on the reference's public env attributes, so it plays any env that has them; on the device the
+    same rule is ``BatchedJssEnv.policy / rollout / lookahead(kind="weighted", weights=rule.weights)``, bit for bit, and
+    ``run_episode`` on a jssenv_amd env plays the episode there (``jss_rule_rollout``)."""
+
+    kind = "weighted"
+
+    def __init__(self, weights, name: str = "weighted", explore: float = 0.0):
+        w = np.asarray(weights)
+        if w.shape != (8,) or w.dtype.kind not in "iu" or (w.astype(np.int64) != w.astype(np.int64).astype(np.int32)).any():
+            raise ValueError("weights: 8 integers in the int32 range")
+        super().__init__(name, f"{name} - among the legal jobs, start the one with the largest weighted score")
+        self.weights = w.astype(np.int32)
+        self.explore = float(explore)
+
+    def _features(self, env, job: int):
+        todo, M = int(env.todo_time_step_job[job]), env.machines
+        durs = [int(env.instance_matrix[job][op][1]) for op in range(M)]
+        return (durs[todo], durs[todo + 1] if todo + 1 < M else 0, sum(durs[todo:]), sum(durs), M - todo,
+                int(env.idle_time_jobs_last_op[job]), int(env.total_idle_time_jobs[job]))
+
+    def _value(self, env, job: int) -> int:
+        return _wrap64(sum(int(w) * x for w, x in zip(self.weights[:7], self._features(env, job))))
+
+    def __call__(self, env) -> int:
+        legal_actions = env.get_legal_actions()
+        jobs = [j for j in range(env.jobs) if legal_actions[j]]
+        if not jobs:
+            return env.jobs if legal_actions[env.jobs] else -1
+        best, best_v = -1, None
+        for j in jobs:
+            v = self._value(env, j)
+            if best_v is None or v > best_v:
+                best, best_v = j, v
+        if legal_actions[env.jobs]:
+            bias = int(self.weights[RW_NOPE])
+            if bias != NEVER_NOPE and bias > best_v:
+                best = env.jobs
+            if self.explore > 0.0 and np.random.random() < self.explore:
+                best = env.jobs
+        return best
+
+    def run_episode(self, env, device_rng: bool = False, seed: Optional[int] = None) -> Tuple[float, int]:
+        """On a jssenv_amd env the episode is one ``jss_rule_rollout`` -- always when the rule draws nothing (``explore == 0``:
+        the host loop would play the same actions), with ``device_rng=True`` otherwise; any other env takes the host loop."""
+        if hasattr(env, "_b") and (device_rng or self.explore == 0.0):
+            return env._run_rule("weighted", explore=self.explore, seed=seed, weights=self.weights)
+        if device_rng:
+            raise ValueError("device_rng=True needs a jssenv_amd.JssEnv")
+        return super().run_episode(env)
+
+
+def evaluate_weights(instances, weights, device=None, explore: float = 0.0, seed: int = 0, _backend=None):
+    """Makespans of a population of weighted rules: ``weights`` is (P, 8) int32 -- a NumPy array, or a tensor on the host or on
+    the device --, ``instances`` one instance or a list of N; one env per (weight row, instance) -- row-major, so the result,
+    a NumPy int64 array, has shape (P, N) -- is reset and played to the end by one ``jss_rule_rollout``.  The inner loop of an
+    evolution strategy / GA / GP over linear rules, in one call.  ``device``: as for ``BatchedJssEnv`` ('cpu' = the host twin).
+
+    Every call builds its batch anew (allocation, upload of the instances, reset) and copies the makespans back: a loop over
+    generations that wants neither keeps one ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and
+    ``rollout("weighted", weights=w, autoreset=False)`` on it with ``w`` on the device -- the two lines this function ends in."""
+    from .env import BatchedJssEnv
+    from .instances import Instance, builtin_instance
+    one = isinstance(instances, (str, Instance))
+    insts = [instances] if one else list(instances)
+    insts = [builtin_instance(i) if isinstance(i, str) else i for i in insts]
+    w = weights if hasattr(weights, "repeat_interleave") else np.ascontiguousarray(np.asarray(weights))
+    if len(w.shape) != 2 or w.shape[1] != 8 or str(w.dtype).split(".")[-1] != "int32":
+        raise ValueError("weights: an int32 array or tensor of shape (P, 8)")
+    P, N = int(w.shape[0]), len(insts)
+    if P == 0 or N == 0:
+        return np.zeros((P, N), dtype=np.int64)
+    kw = {"_backend": _backend} if _backend is not None else {"device": device}
+    if N == 1:
+        env = BatchedJssEnv(insts[0], batch=P, seed=int(seed), **kw)
+        rows = w
+    else:
+        env = BatchedJssEnv(insts, batch=P * N, seed=int(seed), table_of_env=np.arange(P * N, dtype=np.int32) % N, **kw)
+        rows = w.repeat_interleave(N, dim=0) if hasattr(w, "repeat_interleave") else np.repeat(w, N, axis=0)
+    if hasattr(rows, "repeat_interleave") and getattr(env.backend, "torch", None) is None:
+        rows = rows.detach().cpu().numpy()                                # a tensor, and the host twin's NumPy memory
+    env.reset()
+    chunk = env.jmax * env.mmax + 16
+    for _ in range(64):
+        env.rollout("weighted", n_iter=chunk, autoreset=False, explore=explore, weights=rows)
+        if bool(env.backend.numpy(env.done).all()):
+            break
+    else:
+        raise RuntimeError("episodes did not finish")
+    return env.backend.numpy(env.makespan).astype(np.int64).reshape(P, N)
+
+
 DISPATCHING_RULES = {                                                     # dispatching.py:412-420
     "SPT": ShortestProcessingTime(),
     "FIFO": FirstInFirstOut(),
@@ -269,7 +393,9 @@ def compare_rules(env, rules: Optional[List[str]] = None, num_episodes: int = 10
             batch.reset()
             batch.zero_counters()
             for _ in range(64):
-                batch.rollout(device_kind(get_rule(name)), n_iter=chunk, autoreset=False, explore=EXPLORATION_PROBABILITY)
+                rule = get_rule(name)              # (a WeightedRule: its own row and its own exploration rate)
+                batch.rollout(device_kind(rule), n_iter=chunk, autoreset=False, weights=getattr(rule, "weights", None),
+                              explore=getattr(rule, "explore", EXPLORATION_PROBABILITY))
                 if bool(batch.backend.numpy(batch.done).all()):
                     break
             else:

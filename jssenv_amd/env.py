@@ -613,7 +613,7 @@ class BatchedJssEnv:
 
     # -- search: candidate moves scored by rule rollouts (jss_lookahead, include/jss_search.h) ----------------------------
     def lookahead(self, kind: Union[str, int] = "SPT", actions=None, parents=None, n_iter: Optional[int] = None,
-                  seed: Optional[int] = None, explore: float = 0.0, id_base: int = 0):
+                  seed: Optional[int] = None, explore: float = 0.0, id_base: int = 0, weights=None):
         """Score candidate moves without cloning: candidate k starts from env ``parents[k]``, takes ``actions[k]`` (job, J =
         NOPE, -1 = none) and then follows the rule ``kind`` to the end of the episode, on the device, in registers; the batch
         is not touched.  Exactly what ``fork([parents[k]], env_id_base=id_base + k)``, ``step(actions[k])`` and
@@ -625,7 +625,9 @@ class BatchedJssEnv:
         ``reward_num / max_time_op`` of the parent (float32).  ``parents`` / ``actions``: host or device int sequences of
         equal length -> shape ``(n,)``; both None: every action of every env, parent-major, built on the device -> shape
         ``(B, jmax + 1)`` (illegal and padded columns -1).  ``n_iter=None``: ``3 * jmax * mmax``, enough to finish any
-        episode.  A batch dealt out by shape class is evaluated in one launch on the padded extents' kernel."""
+        episode.  A batch dealt out by shape class is evaluated in one launch on the padded extents' kernel.
+        ``weights`` (with ``kind="weighted"``): the continuation follows the caller's weighted rule (``jss_rule_lookahead``,
+        see ``policy``), candidate k with the row of ``parents[k]``."""
         if not self._is_reset:
             raise RuntimeError("call reset() before lookahead()")
         self._no_open_session("lookahead")
@@ -636,7 +638,8 @@ class BatchedJssEnv:
             _abi.bind_search(be.lib)
         t = getattr(be, "torch", None)
         B, A = self.batch, self.jmax + 1
-        k = _abi.policy_code(kind)
+        rule = self._rule_arg(kind, weights, "lookahead")
+        k = None if rule else _abi.policy_code(kind)
         n_iter = 3 * self.jmax * self.mmax if n_iter is None else int(n_iter)
         with be.on_device():
             if parents is None:
@@ -659,10 +662,10 @@ class BatchedJssEnv:
             if n:
                 p = be.ptr
                 la = _abi.JssLookahead(n, p(par), p(act), int(id_base), p(makespan), p(steps), p(rnum))
-                rc = be.lib.jss_lookahead(C.byref(self._desc), C.byref(self._state), C.byref(la), k,
-                                          self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter,
-                                          be.stream())
-                _abi.check(be.lib, rc, "jss_lookahead")
+                call = be.lib.jss_rule_lookahead if rule else be.lib.jss_lookahead
+                rc = call(C.byref(self._desc), C.byref(self._state), C.byref(la), C.byref(rule[0]) if rule else k,
+                          self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter, be.stream())
+                _abi.check(be.lib, rc, "jss_rule_lookahead" if rule else "jss_lookahead")
             # the return: reward numerators over the parent's max_time_op (0 where nothing was evaluated)
             if t is not None:
                 mto = self.env_const[:, _abi.C_MAX_TIME_OP].to(t.float64)[par.long().clamp(0, max(B - 1, 0))] if B else \
@@ -674,7 +677,7 @@ class BatchedJssEnv:
                 ret = np.where(mto > 0, rnum / np.maximum(mto, 1), 0.0).astype(np.float32)
         return makespan.reshape(shape), steps.reshape(shape), ret.reshape(shape)
 
-    def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False):
+    def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the
         rule to the end), and each env takes the action with the lowest makespan -- ties to the lowest index, -1 scores
         count as +inf.  An env none of whose actions can be scored (it is done) is left alone (``JSS_ACTION_SKIP``), or reset
@@ -682,7 +685,7 @@ class BatchedJssEnv:
         taken, ``info["scores"]`` the (B, jmax + 1) makespans."""
         be = self.backend
         t = getattr(be, "torch", None)
-        scores, _, _ = self.lookahead(kind, seed=seed)
+        scores, _, _ = self.lookahead(kind, seed=seed, weights=weights)
         none = _abi.ACTION_RESET if autoreset else _abi.ACTION_SKIP
         with be.on_device():
             if t is not None:
@@ -695,6 +698,42 @@ class BatchedJssEnv:
                 action = np.where(free.all(axis=1), none, best).astype(np.int32)
         obs, reward, done, truncated, _ = self.step(action)
         return obs, reward, done, truncated, {"action": action, "scores": scores}
+
+    # -- caller-weighted rules (include/jss_rules.h) --------------------------------------------------------------------
+    def _stock_code(self, kind, what):
+        """policy_code for the calls that know the stock rules only."""
+        if kind == "weighted":
+            raise NotImplementedError(f"{what} has no weighted-rule form: policy, rollout, lookahead and pilot_step take weights=")
+        return _abi.policy_code(kind)
+
+    def _rule_arg(self, kind, weights, what):
+        """None for a stock ``kind``; for ``kind="weighted"`` the ``(JssRule, array kept alive)`` of ``weights``: an int32
+        tensor or array of shape (8,) -- one row for every env -- or (B, 8) -- env i uses row i --, on the host or on the env's
+        device.  Anything else raises ValueError."""
+        if kind != "weighted":
+            if weights is not None:
+                raise ValueError(f"{what}: weights= goes with kind='weighted'")
+            return None
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError(f"{what}: weighted rules do not run while a step session is open on the env")
+        be = self.backend
+        dt = getattr(weights, "dtype", None)
+        if dt is None or str(dt).split(".")[-1] != "int32":
+            raise ValueError(f"{what}: weights must be an int32 tensor or array of shape (8,) or ({self.batch}, 8) -- "
+                             "quantise float weights yourself (scale, round)")
+        shape = tuple(weights.shape)
+        if shape != (_abi.RW_N,) and shape != (self.batch, _abi.RW_N):
+            raise ValueError(f"{what}: weights must have shape (8,) or ({self.batch}, 8), got {shape}")
+        if not hasattr(be.lib, "jss_rule_policy"):
+            raise RuntimeError(f"{what}: the loaded library does not export the jss_rule_* calls of include/jss_rules.h")
+        if be.lib.jss_rule_policy.argtypes is None:                      # a library bound without include/jss_rules.h so far
+            _abi.bind_rules(be.lib)
+        w = be.as_device(weights, "int32")
+        if getattr(be, "torch", None) is None:
+            w = np.array(w, copy=True)                                   # (as_device keeps one array alive: this one is ours)
+        elif be.ptr(w) % 16:
+            w = w.clone()                                                # (a view at an odd offset: rows are read 16 bytes at a time)
+        return _abi.JssRule(be.ptr(w), _abi.RW_N if len(shape) == 2 else 0), w
 
     # -- raw ABI handles (bench.py launches through these) -------------------------------
     @property
@@ -792,15 +831,29 @@ class BatchedJssEnv:
         return self._hole
 
     def policy(self, kind: Union[str, int] = "random", seed: Optional[int] = None, explore: float = 0.0,
-               cr_factor: Optional[float] = None):
+               cr_factor: Optional[float] = None, weights=None):
         """Per-env action from the on-device selectors (random masked, FIFO, SPT, MWR, LWR, MOR, LOR, CR).
         Returns the env's own (B,) int32 action buffer (overwritten by the next policy() call).
         ``cr_factor``: CriticalRatio(due_date_factor=...) with ANY positive float (dispatching.py:337-360) -- the selector then
         evaluates the reference's float64 expression itself (JSS_POLICY_CR_F64); without it "CR" is the default 1.5, and
-        ``_abi.cr_kind(f)`` codes the factors p / 2^k that also run inside the fused rollouts."""
+        ``_abi.cr_kind(f)`` codes the factors p / 2^k that also run inside the fused rollouts.
+        ``kind="weighted"`` with ``weights``: the caller's rule (``jss_rule_policy``, include/jss_rules.h) -- the legal job
+        with the largest integer score ``sum_f weights[f] * x_f(job)`` over SPT's, MWR's, MOR's, FIFO's ... quantities, NOPE by
+        its bias ``weights[7]``; one int32 row of 8 for every env, or (B, 8): a population, env i with row i.  A batch dealt
+        out by shape class runs on the padded extents' kernel."""
         if not self._is_reset:
             raise RuntimeError("call reset() before policy()")
         be = self.backend
+        rule = self._rule_arg(kind, weights, "policy")
+        if rule:
+            if cr_factor is not None:
+                raise ValueError("cr_factor is CriticalRatio's due-date factor: a positive float, with kind 'CR'")
+            d, s, _ = self._refs()
+            with be.on_device():
+                _abi.check(be.lib, be.lib.jss_rule_policy(d, s, C.byref(rule[0]), self.seed if seed is None else int(seed),
+                                                          int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()),
+                           "jss_rule_policy")
+            return self._actions_out
         k = _abi.policy_code(kind)
         if cr_factor is not None:
             if (k & 0xFF) != _abi.POLICY["CR"] or not 0.0 < float(cr_factor) < 1e300:
@@ -912,11 +965,25 @@ class BatchedJssEnv:
         return info
 
     def rollout(self, kind: Union[str, int] = "random", n_iter: int = 1, seed: Optional[int] = None,
-                autoreset: bool = True, explore: float = 0.0):
-        """n_iter x (policy + step) per env in ONE launch (state stays in registers)."""
+                autoreset: bool = True, explore: float = 0.0, weights=None):
+        """n_iter x (policy + step) per env in ONE launch (state stays in registers).  ``kind="weighted"`` with
+        ``weights``: the caller's rule (``jss_rule_rollout``; see ``policy``) -- with one row per env, a population of rules
+        plays its episodes in one launch.  On a batch of generated instances with ``fresh=True`` the weighted form takes
+        ``autoreset=False`` only, also for one iteration (the stock form regenerates the envs found done first)."""
         if not self._is_reset:
             raise RuntimeError("call reset() before rollout()")
         be = self.backend
+        rule = self._rule_arg(kind, weights, "rollout")
+        if rule:
+            flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
+            d, s, o = self._refs()
+            if autoreset and self.fresh:
+                self._refuse_fresh("rollout(kind='weighted', autoreset=True)")
+            with be.on_device():
+                rc = be.lib.jss_rule_rollout(d, s, o, C.byref(rule[0]), self.seed if seed is None else int(seed),
+                                             int(round(explore * 65536)), int(n_iter), flags, be.stream())
+                _abi.check(be.lib, rc, "jss_rule_rollout")
+            return self._obs(), self.reward, self.done, False, {}
         k = _abi.policy_code(kind)
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         d, s, o = self._refs()
@@ -949,7 +1016,7 @@ class BatchedJssEnv:
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
-        k = _abi.policy_code(kind)
+        k = self._stock_code(kind, "rollout_steps")
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         d, s, o = self._refs()
         sd = self.seed if seed is None else int(seed)
@@ -983,7 +1050,7 @@ class BatchedJssEnv:
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
-        k = _abi.policy_code(kind)
+        k = self._stock_code(kind, "policy_step_steps")
         flags = (_abi.ROLLOUT_AUTORESET if autoreset else 0)
         d, s, o = self._refs()
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
@@ -1013,7 +1080,7 @@ class BatchedJssEnv:
         be = self.backend
         if not hasattr(be, "stream_array"):
             return lambda: self.rollout_steps(kind, steps, n_sub, seed, autoreset, explore)
-        k = _abi.policy_code(kind)
+        k = self._stock_code(kind, "bind_rollout_steps")
         flags = (_abi.ROLLOUT_AUTORESET if autoreset else 0) | (0 if caller_orders_streams else _abi.ROLLOUT_FORK_JOIN)
         d, s, o = self._refs()
         with be.on_device():
@@ -1066,7 +1133,7 @@ class BatchedJssEnv:
                 shape, dtype = shapes[name]
                 t = None if buffers is None else buffers.get(name)
                 out[name] = t if t is not None and tuple(t.shape) == shape else be.zeros(shape, dtype)
-        k = _abi.policy_code(kind)
+        k = self._stock_code(kind, "trajectory")
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
         # (by shape class: one launch per range of the batch -- below 64 jobs / the rest -- each with the kernel of ITS shape,
