@@ -83,6 +83,12 @@ RULES_SYMBOLS = ("jss_rule_policy", "jss_rule_rollout", "jss_rule_lookahead")
 RW_DUR, RW_NEXT, RW_REM, RW_TOTAL, RW_OPS, RW_WAIT, RW_IDLE, RW_NOPE, RW_N = 0, 1, 2, 3, 4, 5, 6, 7, 8
 RW_NEVER_NOPE = -2**31
 
+# include/jss_keys.h: the companion header of the per-operation priority keys (its own version).  The key selector has no POLICY
+# code either: it is reached through these symbols only.
+KEYS_VERSION = 1
+KEYS_SYMBOLS = ("jss_key_policy", "jss_key_rollout", "jss_key_lookahead")
+KEY_NEVER_NOPE = -2**31            # JssKeys.nope_key that exceeds no key: NOPE only when no job is legal
+
 _p = C.c_void_p
 
 
@@ -134,6 +140,10 @@ class JssLookahead(C.Structure):     # include/jss_search.h
 
 class JssRule(C.Structure):          # include/jss_rules.h
     _fields_ = [("weights", _p), ("stride", C.c_int32)]
+
+
+class JssKeys(C.Structure):          # include/jss_keys.h
+    _fields_ = [("keys", _p), ("stride", C.c_int32), ("nope_key", C.c_int32)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -219,6 +229,20 @@ def bind_rules(lib):
     lib.jss_rule_rollout.argtypes = [D, S, O, R, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _p]
     lib.jss_rule_lookahead.restype = C.c_int
     lib.jss_rule_lookahead.argtypes = [D, S, C.POINTER(JssLookahead), R, C.c_uint64, C.c_uint32, C.c_int32, _p]
+    return lib
+
+
+def bind_keys(lib):
+    """Attach the prototypes of include/jss_keys.h; raises AttributeError naming the first missing symbol."""
+    for name in KEYS_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    D, S, O, K = C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssOut), C.POINTER(JssKeys)
+    lib.jss_key_policy.restype, lib.jss_key_policy.argtypes = C.c_int, [D, S, K, C.c_uint64, C.c_uint32, _p, _p]
+    lib.jss_key_rollout.restype = C.c_int
+    lib.jss_key_rollout.argtypes = [D, S, O, K, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _p]
+    lib.jss_key_lookahead.restype = C.c_int
+    lib.jss_key_lookahead.argtypes = [D, S, C.POINTER(JssLookahead), K, C.c_uint64, C.c_uint32, C.c_int32, _p]
     return lib
 
 

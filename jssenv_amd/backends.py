@@ -40,6 +40,8 @@ class HipBackend:
         self.lib = _abi.bind_search(_abi.bind(C.CDLL(path)))
         if all(hasattr(self.lib, name) for name in _abi.RULES_SYMBOLS):   # (a build of the v14 ABI older than include/jss_rules.h
             _abi.bind_rules(self.lib)                                     #  still serves everything else: its first weighted call raises)
+        if all(hasattr(self.lib, name) for name in _abi.KEYS_SYMBOLS):    # (likewise for include/jss_keys.h)
+            _abi.bind_keys(self.lib)
         if not self.lib.jss_backend().startswith(b"hip"):
             raise RuntimeError(f"{path} is not the HIP library ({self.lib.jss_backend()!r})")
         self._scalars = {}
@@ -228,7 +230,7 @@ class CpuBackend:
             if not os.path.isfile(path):
                 raise RuntimeError(f"device='cpu' needs {path}: build it with `g++ -O3 -std=c++17 -fopenmp -fPIC -shared "
                                    f"-Iinclude jssenv_amd/csrc/jss_cpu.cpp -o {path}` (automatic build failed: {exc})") from exc
-        self.lib = _abi.bind_rules(_abi.bind_search(_abi.bind(C.CDLL(path))))
+        self.lib = _abi.bind_keys(_abi.bind_rules(_abi.bind_search(_abi.bind(C.CDLL(path)))))
         if not self.lib.jss_backend().startswith(b"cpu"):
             raise RuntimeError(f"{path} is not the CPU twin ({self.lib.jss_backend()!r})")
         self.threads = int(threads)

@@ -46,6 +46,8 @@ def shape_class(jobs: int, machines: int) -> int:
 def _stock_kind(kind):
     if kind == "weighted":
         raise NotImplementedError("BucketedJssEnv knows the stock rules only: weighted rules run on BatchedJssEnv (weights=)")
+    if kind == "keys":
+        raise NotImplementedError("BucketedJssEnv knows the stock rules only: key tables run on BatchedJssEnv (keys=)")
     return kind
 
 

@@ -21,6 +21,7 @@ CPU_FLAGS = ["-O3", "-std=c++17", "-fopenmp", "-fPIC", "-shared", "-Wall", "-I" 
 _HEADER = os.path.join(_ROOT, "include", "jss_hip.h")
 _SEARCH = os.path.join(_ROOT, "include", "jss_search.h")     # its companion: the search calls (jss_lookahead)
 _RULES = os.path.join(_ROOT, "include", "jss_rules.h")       # ... and the caller-weighted rules (jss_rule_*)
+_KEYS = os.path.join(_ROOT, "include", "jss_keys.h")         # ... and the per-operation priority keys (jss_key_*)
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -38,7 +39,7 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))] + [_HEADER, _SEARCH, _RULES]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))] + [_HEADER, _SEARCH, _RULES, _KEYS]
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -46,7 +47,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

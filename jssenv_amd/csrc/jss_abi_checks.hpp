@@ -12,6 +12,7 @@
 #include "jss_hip.h"
 #include "jss_search.h"
 #include "jss_rules.h"
+#include "jss_keys.h"
 
 namespace jss_abi {
 
@@ -321,6 +322,36 @@ inline int check_rule_lookahead(const JssDesc *d, const JssState *s, const JssLo
     if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
     if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
     return check_rule(d, rule);
+}
+
+// ---- per-operation priority keys (include/jss_keys.h) ----------------------------------------------------------------
+// a JssKeys, where its call's namesake checks `kind` (the selector reads no table of the batch's own: JssDesc.rem may be NULL)
+inline int check_keys(const JssDesc *d, const JssKeys *keys) {
+    if (!keys || !keys->keys) return JSS_E_NULL;
+    return keys->stride == 0 || keys->stride == d->jmax * d->mmax ? 0 : JSS_E_SHAPE;
+}
+
+inline int check_key_policy(const JssDesc *d, const JssState *s, const JssKeys *keys, const int32_t *actions) {
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!actions) return JSS_E_NULL;
+    return check_keys(d, keys);
+}
+
+inline int check_key_rollout(const JssDesc *d, const JssState *s, const JssOut *o, const JssKeys *keys, int32_t n_iter) {
+    int rc = check_args(d, s, o, true);
+    if (rc) return rc;
+    if ((rc = check_keys(d, keys))) return rc;
+    return n_iter < 0 ? JSS_E_SHAPE : 0;
+}
+
+inline int check_key_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, const JssKeys *keys, int32_t n_iter) {
+    if (!d || !s || !la) return JSS_E_NULL;
+    int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
+    if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
+    return check_keys(d, keys);
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -43,6 +43,7 @@
 #include "jss_hip.h"
 #include "jss_search.h"
 #include "jss_rules.h"
+#include "jss_keys.h"
 
 namespace jss {
 
@@ -107,7 +108,10 @@ struct Params {
     int32_t norm_slot_ints;           // packed kernel, kTabGlobal: ints between two slots' normaliser tables
     JssLogits lg;                     // kLogits (row resolved: >= jmax + 1)
     JssLookahead la;                  // kLookahead: the candidates (the grid covers la.n, the batch is where the data comes from)
-    JssRule rule;                     // kind == kKindWeighted (jss_rule_*, include/jss_rules.h): the caller's weight rows
+    union {                           // 16 bytes either way: one slot of the arguments, one stash in LDS (rule_stash)
+        JssRule rule;                 // kind == kKindWeighted (jss_rule_*, include/jss_rules.h): the caller's weight rows
+        JssKeys keys;                 // kind == kKindKeys (jss_key_*, include/jss_keys.h): the caller's key tables
+    };
 #ifdef JSS_PROFILING
     unsigned long long *stamps;       // instrumented builds: [B][16] shader-clock stamps of the one-wavefront-per-env kernels (JSS_STAMP)
 #endif
@@ -422,6 +426,9 @@ constexpr double kCrInf = __builtin_huge_val();
 // The selector is compiled into the modes those calls launch and into no other (rule_mode: a template flag of p_select /
 // select_action, as F64 is): jss_rule_rollout plans kRollout for every n_iter, so the one-step kernels never carry it.
 constexpr int kKindWeighted = JSS_N_POLICIES;
+// ... and of the jss_key_* calls (include/jss_keys.h): the same instantiations carry the key selector, behind the same flag
+constexpr int kKindKeys = JSS_N_POLICIES + 1;
+static_assert(sizeof(JssKeys) == sizeof(JssRule) && sizeof(JssKeys) == 16, "JssKeys shares JssRule's slot of Params and of LDS");
 constexpr bool rule_mode(int mode) { return mode == kPolicy || mode == kRollout || mode == kLookahead; }
 // one term of a job's score: the product is exact in int64 (two int32 factors); the SUM wraps, so it is kept unsigned
 __device__ __forceinline__ unsigned long long rw_term(int w, int x) { return (unsigned long long)((long long)w * (long long)x); }
@@ -457,6 +464,13 @@ __device__ __forceinline__ unsigned wave_umax(unsigned v) {
 #else
 #define JSS_SCHED_FENCE() do {} while (0)
 #endif
+// a register the optimiser knows nothing about: what is computed from it stays where it is written, inside its branch, and is
+// not hoisted out of the step loop into a register of its own (host pass and the test emulator: nothing)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JSS_OPAQUE(x) asm volatile("" : "+v"(x))
+#else
+#define JSS_OPAQUE(x) do {} while (0)
+#endif
 // Where a packed kernel's weighted branch finds the JssRule: kRwArg = in the Params as the kernel reads them (the kernels that
 // read their arguments in place, and the one-launch policy kernel); kRwLds = in LDS.  The shared-table rollout / lookahead
 // kernels take their arguments by value (JSS_PARAMS_OF): there the rule's three dwords would sit in SGPRs through the whole step
@@ -473,12 +487,14 @@ __device__ __forceinline__ int32_t *rule_stash() {
     __shared__ int32_t stash[4];
     return stash;
 }
-__device__ __forceinline__ void rule_stash_put(const JssRule &rule) {
+// (the slot of Params as a JssKeys: a JssRule is its first three words, the fourth, free with a rule, holds nope_key)
+__device__ __forceinline__ void rule_stash_put(const JssKeys &keys) {
     int32_t *st = rule_stash();
-    const unsigned long long w = (unsigned long long)rule.weights;
+    const unsigned long long w = (unsigned long long)keys.keys;
     st[0] = (int)(unsigned)w;
     st[1] = (int)(unsigned)(w >> 32);
-    st[2] = rule.stride;
+    st[2] = keys.stride;
+    st[3] = keys.nope_key;
 }
 __device__ __forceinline__ bool rw_nope(int w_nope, long long best) { return w_nope != JSS_RW_NEVER_NOPE && (long long)w_nope > best; }
 

@@ -49,8 +49,10 @@ struct Call {   // one ABI call
     int flags = 0;
     JssLogits lg = JssLogits();   // jss_step_logits (row resolved)
     JssRule rule = JssRule();     // kind == kKindWeighted (jss_rule_*, include/jss_rules.h)
+    JssKeys keys = JssKeys();     // kind == kKindKeys (jss_key_*, include/jss_keys.h)
 };
 constexpr int kKindWeighted = JSS_N_POLICIES;   // Call.kind of the jss_rule_* calls: no public JSS_POLICY_* code
+constexpr int kKindKeys = JSS_N_POLICIES + 1;   // ... and of the jss_key_* calls
 
 // One env: pointers into the batch tensors + its instance.
 struct Env {
@@ -458,7 +460,25 @@ int select_weighted(const Env &e, const Call &c, int row) {
     return best;
 }
 
-// row: the env's index in the call's batch (the weighted rules' row)
+// include/jss_keys.h: key(j) = keys[row][j][ops job j has completed], a table over the batch's padded extents; the legal job
+// with the largest key, the lowest index on ties; NOPE where it is legal and nope_key exceeds the best key.
+int select_keys(const Env &e, const Call &c, int row) {
+    const int32_t *k = c.keys.keys + (size_t)row * c.keys.stride;
+    int best = -1;
+    int32_t best_key = 0;
+    for (int j = 0; j < e.J; ++j) {
+        if (!e.legal(j)) continue;
+        const int32_t key = k[(size_t)j * c.d.mmax + e.todo(j)];
+        if (best < 0 || key > best_key) {
+            best = j;
+            best_key = key;
+        }
+    }
+    if (e.noop() && c.keys.nope_key > best_key) best = e.J;
+    return best;
+}
+
+// row: the env's index in the call's batch (the weighted rules' row, the key tables' table)
 int select_action(const Env &e, const Call &c, uint64_t env_id, int row) {
     const uint32_t episode = (uint32_t)e.hdr[JSS_H_EPISODE], step = (uint32_t)e.hdr[JSS_H_STEP];
     const int nl = n_legal(e);
@@ -479,7 +499,8 @@ int select_action(const Env &e, const Call &c, uint64_t env_id, int row) {
     const bool cr_f64 = kind == JSS_POLICY_CR && ((c.kind >> 24) & 1);    // JSS_POLICY_CR_F64: the reference's doubles themselves
     double best_ratio = 0.0;
     if (kind == kKindWeighted) best = select_weighted(e, c, row);
-    for (int j = 0; j < e.J && kind != kKindWeighted; ++j) {
+    if (kind == kKindKeys) best = select_keys(e, c, row);
+    for (int j = 0; j < e.J && kind < kKindWeighted; ++j) {
         if (!e.legal(j)) continue;
         const int todo = e.todo(j);
         if (cr_f64) {                                                     // dispatching.py:351-363, :391-399
@@ -1200,6 +1221,36 @@ int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLook
     if (const int rc = check_rule_lookahead(desc, state, la, rule, n_iter)) return rc;
     Call c;
     c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kKindWeighted; c.rule = *rule; c.seed = seed; c.explore_q16 = explore_q16;
+    c.n_iter = n_iter;
+    const JssLookahead l = *la;
+    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
+    return 0;
+}
+
+// include/jss_keys.h: the namesakes' calls with Call.kind = kKindKeys and the key tables
+int jss_key_policy(const JssDesc *desc, const JssState *state, const JssKeys *keys, uint64_t seed, uint32_t explore_q16,
+                   int32_t *actions, void *) {
+    if (const int rc = check_key_policy(desc, state, keys, actions)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kKindKeys; c.keys = *keys; c.seed = seed;
+    c.explore_q16 = explore_q16;
+    return run(c, kPolicy);
+}
+
+int jss_key_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssKeys *keys, uint64_t seed,
+                    uint32_t explore_q16, int32_t n_iter, int32_t flags, void *) {
+    if (const int rc = check_key_rollout(desc, state, out, keys, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = *out; c.kind = kKindKeys; c.keys = *keys; c.seed = seed; c.explore_q16 = explore_q16;
+    c.n_iter = n_iter; c.flags = flags;
+    return run(c, kRollout);
+}
+
+int jss_key_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssKeys *keys,
+                      uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *) {
+    if (const int rc = check_key_lookahead(desc, state, la, keys, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kKindKeys; c.keys = *keys; c.seed = seed; c.explore_q16 = explore_q16;
     c.n_iter = n_iter;
     const JssLookahead l = *la;
     parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });

@@ -981,4 +981,32 @@ int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLook
     return launch_lookahead(p, stream);
 }
 
+// Per-operation priority keys (include/jss_keys.h): the same launches with Params.kind = kKindKeys and the key tables, in the
+// kernels that carry the weighted selector.  jss_key_rollout plans kRollout whatever n_iter is, as jss_rule_rollout does.
+int jss_key_policy(const JssDesc *desc, const JssState *state, const JssKeys *keys, uint64_t seed, uint32_t explore_q16,
+                   int32_t *actions, void *stream) {
+    if (const int rc = check_key_policy(desc, state, keys, actions)) return rc;
+    Params p = params_of(desc, state, nullptr);
+    p.actions_out = actions; p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16;
+    return launch<kPolicy>(p, stream);
+}
+
+int jss_key_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssKeys *keys, uint64_t seed,
+                    uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
+    if (const int rc = check_key_rollout(desc, state, out, keys, n_iter)) return rc;
+    Params p = params_of(desc, state, out);
+    p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16;
+    p.n_iter = n_iter; p.flags = flags;
+    return launch<kRollout>(p, stream);
+}
+
+int jss_key_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssKeys *keys,
+                      uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *stream) {
+    if (const int rc = check_key_lookahead(desc, state, la, keys, n_iter)) return rc;
+    if (la->n == 0) return 0;
+    Params p = params_of(desc, state, nullptr);
+    p.la = *la; p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
+    return launch_lookahead(p, stream);
+}
+
 }  // extern "C"

@@ -482,7 +482,8 @@ __device__ __forceinline__ int p_step(PEnv<G> &e, const PCtx<G, TAB> &c, const P
 // ---------------------------------------------------------------------------------------
 // F64: the instantiation also carries JSS_POLICY_CR_F64's float64 selector (the policy kernels only)
 // RW: ... and the caller-weighted selector (include/jss_rules.h; rule_mode: kPolicy / kRollout / kLookahead), with the rule found
-// where rule_source says.  Every lane reads its env's row itself, in the branch: nothing of the rule is live outside it.
+// where rule_source says.  Every lane reads its env's row itself, in the branch: nothing of the rule is live outside it.  The same
+// flag carries the per-operation key selector (include/jss_keys.h, kind == kKindKeys), whose JssKeys lies where the JssRule does.
 template <int G, int TAB, bool F64 = false, int RW = kRwNo>
 __device__ __forceinline__ int p_select(const PEnv<G> &e, const PCtx<G, TAB> &c, const Params &p, uint64_t env_id,
                                         uint32_t episode, uint32_t step) {
@@ -539,6 +540,32 @@ __device__ __forceinline__ int p_select(const PEnv<G> &e, const PCtx<G, TAB> &c,
             const uint32_t hit = grp_ballot<G>(top && sl == lo, c.gbase);
             a = hit ? __ffs(hit) - 1 : c.J;                              // ties: the lowest job index; no job legal: NOPE
             if (hit && e.noop && rw_nope(wb.w, rw_score(hi, lo))) a = c.J;
+        } else if (RW && kind == kKindKeys) {
+            // include/jss_keys.h: one dword of my env's table, [gl][todo], at a per-lane 64-bit address formed here (batch x jmax x
+            // mmax x 4 bytes passes 2^32); a lane whose job is not legal reads nothing (padded entries are never touched) and is
+            // told apart by its own predicate below, since every int32 is a key.  Nothing of the table is live outside the branch.
+            const int32_t *kb;
+            unsigned kstride;
+            int nope_key;
+            if (RW == kRwLds) {
+                const int32_t *st = rule_stash();
+                kb = reinterpret_cast<const int32_t *>((unsigned long long)(unsigned)st[1] << 32 | (unsigned)st[0]);
+                kstride = (unsigned)st[2];
+                nope_key = st[3];
+            } else {
+                kb = p.keys.keys;
+                kstride = (unsigned)p.keys.stride;
+                nope_key = p.keys.nope_key;
+            }
+            int gl = c.gl;                                               // (gl x mmax is loop-invariant: formed here, not held)
+            JSS_OPAQUE(gl);
+            const unsigned long long at = (unsigned long long)((unsigned)c.first_env + c.rel) * kstride +
+                                          (unsigned)(gl * p.d.mmax + e.todo);
+            const int key = kb[e.legal ? at : 0ull];                     // (no branch around the load: entry 0 is always there)
+            const int best = grp_max<G>(rw_key_hi(key, e.legal));
+            const uint32_t hit = grp_ballot<G>(e.legal && key == best, c.gbase);
+            a = hit ? __ffs(hit) - 1 : c.J;                              // ties: the lowest job index; no job legal: NOPE
+            if (hit && e.noop && nope_key > best) a = c.J;
         } else if (kind == JSS_POLICY_CR) {
             const int total = e.legal ? rem[0] : 0;                      // dispatching.py:373 job length
             const int remaining = e.legal ? rem[e.todo] : 1;             // :391
@@ -1254,7 +1281,8 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if constexpr (rule_source(MODE, TAB) == kRwLds) {                    // (first of all: no load is in flight yet; read behind the
-        if (threadIdx.x == 0) rule_stash_put(p.rule);                    //  barrier that follows the op table's staging)
+        if (threadIdx.x == 0) rule_stash_put(p.keys);                    //  barrier that follows the op table's staging; a JssRule
+                                                                         //  is the first three words of the same slot)
     }
     // obs image of this wave: E * jmax * 7 floats, 16-byte aligned (table_lds_ints is a multiple of 4)
     float *scratch = reinterpret_cast<float *>(lds + p.table_lds_ints) + wave * p.obs_wave_floats;

@@ -479,7 +479,8 @@ __device__ __forceinline__ int nth_set_bit(uint64_t mask, int n, int lane) {
 
 // F64: the instantiation also carries JSS_POLICY_CR_F64's float64 selector (the policy kernels only)
 // RW: ... and the caller-weighted selector (include/jss_rules.h; rule_mode: kPolicy / kRollout / kLookahead).  The env's weight
-// row is wave-uniform: scalar loads at a wave-uniform address, the weights sit in SGPRs while the lanes form their scores.
+// row is wave-uniform: scalar loads at a wave-uniform address, the weights sit in SGPRs while the lanes form their scores.  The same
+// flag carries the per-operation key selector (include/jss_keys.h, kind == kKindKeys).
 template <int JPL, bool F64 = false, bool RW = false>
 __device__ __forceinline__ int select_action(const Env<JPL> &e, const Ctx &c, const Params &p, uint64_t env_id,
                                              uint32_t episode, uint32_t step) {
@@ -545,6 +546,31 @@ __device__ __forceinline__ int select_action(const Env<JPL> &e, const Ctx &c, co
             if (a < 0 && m) a = s * kWave + __ffsll((unsigned long long)m) - 1;
         }
         if (e.noop && rw_nope(w[JSS_RW_NOPE], rw_score(hi, lo))) a = c.J;
+    } else if (RW && kind == kKindKeys) {
+        // include/jss_keys.h: my env's table is wave-uniform, the entry [j][todo] per lane; a slot whose job is not legal reads
+        // nothing.  With two jobs per lane the better of the two slots first (the lower slot on ties: the lower index).
+        const int32_t *kt = p.keys.keys + (size_t)c.b * p.keys.stride;
+        int key = 0, slot = 0;
+        bool part = false;
+#pragma unroll
+        for (int s = 0; s < JPL; ++s) {
+            const int j = s * kWave + c.lane;
+            const bool lg = (e.legal[s] >> c.lane) & 1;
+            const int v = lg ? kt[j * c.stride + e.todo[s]] : 0;
+            if (lg && (!part || v > key)) {
+                key = v;
+                slot = s;
+                part = true;
+            }
+        }
+        const int best = wave_max(rw_key_hi(key, part));
+        const bool hit = part && key == best;
+#pragma unroll
+        for (int s = 0; s < JPL; ++s) {                                  // ties: the lowest job index
+            const uint64_t m = __ballot(hit && slot == s);
+            if (a < 0 && m) a = s * kWave + __ffsll((unsigned long long)m) - 1;
+        }
+        if (e.noop && p.keys.nope_key > best) a = c.J;
     } else if (F64 && kind == JSS_POLICY_CR && ((p.kind >> 24) & 1)) {
         CrKeyF best;
         best.ratio = kCrInf;

@@ -351,6 +351,174 @@ def evaluate_weights(instances, weights, device=None, explore: float = 0.0, seed
     return env.backend.numpy(env.makespan).astype(np.int64).reshape(P, N)
 
 
+# ---- per-operation priority keys (include/jss_keys.h) -------------------------------------------------------------
+# A rule is a table of one int32 key per operation: among the legal jobs, the one whose CURRENT operation has the largest key.
+KEY_NEVER_NOPE = -2**31
+
+
+class KeyRule(DispatchingRule):
+    """A dispatching rule given by a (J, M) int32 table of priorities, one per operation -- the random-key / priority-list
+    encoding of a schedule: among the legal jobs, the one with the largest ``keys[job][ops the job has completed]``, the lowest
+    job index on ties; NOPE when only NOPE is legal, or when it is legal and ``nope_key`` exceeds that key (``None``: never
+    while a job is legal).  Then, where NOPE is legal, NOPE with probability ``explore`` (default 0).
+
+    ``__call__`` reads only the public ``legal_actions`` and ``todo_time_step_job`` of an env, so it plays any env that has
+    them; on the device the same rule is ``BatchedJssEnv.policy / rollout / lookahead(kind="keys", keys=rule.keys,
+    nope_key=rule.nope_key)``, bit for bit, and ``run_episode`` on a jssenv_amd env plays the episode there
+    (``jss_key_rollout``)."""
+
+    kind = "keys"
+
+    def __init__(self, keys, nope_key: Optional[int] = None, name: str = "keys", explore: float = 0.0):
+        k = np.asarray(keys)
+        if k.ndim != 2 or k.dtype.kind not in "iu" or (k.astype(np.int64) != k.astype(np.int64).astype(np.int32)).any():
+            raise ValueError("keys: a (J, M) table of integers in the int32 range")
+        nope = KEY_NEVER_NOPE if nope_key is None else int(nope_key)
+        if not -2**31 <= nope < 2**31:
+            raise ValueError("nope_key: an integer in the int32 range")
+        super().__init__(name, f"{name} - among the legal jobs, start the one whose current operation has the largest key")
+        self.keys = np.ascontiguousarray(k.astype(np.int32))
+        self.nope_key = nope
+        self.explore = float(explore)
+
+    def __call__(self, env) -> int:
+        legal_actions = env.legal_actions
+        J = len(legal_actions) - 1
+        todo = env.todo_time_step_job
+        best, best_key = -1, None
+        for j in range(J):
+            if legal_actions[j]:
+                key = int(self.keys[j][int(todo[j])])
+                if best_key is None or key > best_key:
+                    best, best_key = j, key
+        if best < 0:
+            return J if legal_actions[J] else -1
+        if legal_actions[J]:
+            if self.nope_key > best_key:
+                best = J
+            if self.explore > 0.0 and np.random.random() < self.explore:
+                best = J
+        return best
+
+    def _device_keys(self, env):
+        """the table over a jssenv_amd env's padded extents (they are the instance's own for a B = 1 view)"""
+        if self.keys.shape != (env.jobs, env.machines):
+            raise ValueError(f"keys of shape {self.keys.shape} on an instance of {env.jobs} x {env.machines}")
+        return self.keys
+
+    def run_episode(self, env, device_rng: bool = False, seed: Optional[int] = None) -> Tuple[float, int]:
+        """On a jssenv_amd env the episode is one ``jss_key_rollout`` -- always when the rule draws nothing (``explore == 0``:
+        the host loop would play the same actions), with ``device_rng=True`` otherwise; any other env takes the host loop."""
+        if hasattr(env, "_b") and (device_rng or self.explore == 0.0):
+            return env._run_rule("keys", explore=self.explore, seed=seed, keys=self._device_keys(env), nope_key=self.nope_key)
+        if device_rng:
+            raise ValueError("device_rng=True needs a jssenv_amd.JssEnv")
+        return super().run_episode(env)
+
+
+def _instance_of(instance):
+    from .instances import builtin_instance
+    return builtin_instance(instance) if isinstance(instance, str) else instance
+
+
+def rule_keys(instance, rule: str) -> np.ndarray:
+    """The (J, M) int32 key table that plays what the stock rule ``rule`` plays on ``instance``, for the five stock rules that
+    ARE a table per operation: SPT = -duration, MWR = remaining work, LWR = -remaining work, MOR = M - k, LOR = k - M (k: the
+    operation's index in its job).  FIFO and CriticalRatio rank by the clock, not by the operation: ``ValueError``."""
+    inst = _instance_of(instance)
+    dur = np.asarray(inst.duration, dtype=np.int64)
+    J, M = dur.shape
+    rem = dur[:, ::-1].cumsum(axis=1)[:, ::-1]                            # rem[j][k] = durations of ops k..M-1
+    left = np.broadcast_to(M - np.arange(M, dtype=np.int64), (J, M))
+    tables = {"SPT": -dur, "MWR": rem, "LWR": -rem, "MOR": left, "LOR": -left}
+    if rule not in tables:
+        raise ValueError(f"rule {rule!r} is no table of per-operation keys: one of {sorted(tables)}")
+    return np.ascontiguousarray(tables[rule].astype(np.int32))
+
+
+def keys_from_actions(instance, actions) -> np.ndarray:
+    """An episode's action sequence as a (J, M) int32 key table that reproduces it: the k-th operation of job j gets the key
+    ``-d``, d the index in ``actions`` of the decision that dispatched it; NOPE (``J``) and ``-1`` entries are skipped (so are
+    the ``JSS_ACTION_SKIP`` entries a finished env records); operations never dispatched keep ``-len(actions)``.  ``actions``:
+    one env's record, e.g. ``trajectory(...)["action"][:, i]``.
+
+    Any episode played with NOPE taken only when no job was legal is reproduced decision for decision by
+    ``rollout("keys", keys=...)``: at decision d every other legal job's current operation is dispatched later than d, so it
+    holds a smaller key and the chosen job holds the largest.  An episode with voluntary NOPEs (exploration, a NOPE bias) is
+    not promised: the table says which job goes first, never when to wait."""
+    inst = _instance_of(instance)
+    J, M = inst.jobs, inst.machines
+    acts = np.asarray(actions).reshape(-1)
+    keys = np.full((J, M), -len(acts), dtype=np.int64)
+    done = np.zeros(J, dtype=np.int64)
+    for d, a in enumerate(acts):
+        a = int(a)
+        if a < 0 or a >= J:
+            continue
+        if done[a] >= M:
+            raise ValueError(f"decision {d} dispatches job {a}, which has no operation left")
+        keys[a, done[a]] = -d
+        done[a] += 1
+    return keys.astype(np.int32)
+
+
+def keys_from_floats(x):
+    """The order-preserving map float32 -> int32: ``x < y`` exactly when ``keys_from_floats(x) < keys_from_floats(y)`` as
+    signed integers, -0 and +0 get one key, +-inf are the largest and smallest keys in use; NaN is refused (``ValueError``).  A
+    network's float priorities become key tables without losing an order relation.  NumPy arrays (anything ``np.asarray``
+    takes) and torch tensors, on the device when given a device tensor; other float dtypes are rounded to float32 first."""
+    if hasattr(x, "is_floating_point"):                                  # a torch tensor
+        import torch
+        f = x.to(torch.float32) + 0.0                                     # (-0 + 0 = +0)
+        if bool(torch.isnan(f).any()):
+            raise ValueError("keys_from_floats: NaN has no place in an order")
+        b = f.contiguous().view(torch.int32)
+        return torch.where(b >= 0, b, b ^ 0x7FFFFFFF)
+    f = np.ascontiguousarray(np.asarray(x, dtype=np.float32) + np.float32(0.0))
+    if np.isnan(f).any():
+        raise ValueError("keys_from_floats: NaN has no place in an order")
+    b = f.view(np.int32)
+    return np.where(b >= 0, b, b ^ np.int32(0x7FFFFFFF)).astype(np.int32)
+
+
+def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, explore: float = 0.0, seed: int = 0,
+                  return_solution: bool = False, _backend=None):
+    """Makespans of a population of key tables: ``keys`` is (P, J, M) int32 -- a NumPy array, or a tensor on the host or on the
+    device --, one chromosome per row; one env per table is reset and decoded to the end by one ``jss_key_rollout``.  Returns
+    the (P,) makespans, a NumPy int64 array; with ``return_solution`` also the (P, J, M) start times of the decoded schedules
+    (``start[p][j][k]``: operation k of job j).  The inner loop of a GA / BRKGA / CMA-ES over keys, in one call.  ``device``: as
+    for ``BatchedJssEnv`` ('cpu' = the host twin).
+
+    Every call builds its batch anew, as ``evaluate_weights`` does: a loop over generations keeps one
+    ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and ``rollout("keys", keys=k, autoreset=False)`` on it."""
+    from .env import BatchedJssEnv
+    inst = _instance_of(instance)
+    J, M = inst.jobs, inst.machines
+    k = keys if hasattr(keys, "is_floating_point") else np.ascontiguousarray(np.asarray(keys))
+    if len(k.shape) != 3 or tuple(k.shape[1:]) != (J, M) or str(k.dtype).split(".")[-1] != "int32":
+        raise ValueError(f"keys: an int32 array or tensor of shape (P, {J}, {M})")
+    P = int(k.shape[0])
+    if P == 0:
+        ms = np.zeros((0,), dtype=np.int64)
+        return (ms, np.zeros((0, J, M), dtype=np.int64)) if return_solution else ms
+    kw = {"_backend": _backend} if _backend is not None else {"device": device}
+    env = BatchedJssEnv(inst, batch=P, seed=int(seed), **kw)
+    if hasattr(k, "is_floating_point") and getattr(env.backend, "torch", None) is None:
+        k = k.detach().cpu().numpy()                                      # a tensor, and the host twin's NumPy memory
+    env.reset()
+    chunk = J * M + 16
+    for _ in range(64):
+        env.rollout("keys", n_iter=chunk, autoreset=False, explore=explore, keys=k, nope_key=nope_key)
+        if bool(env.backend.numpy(env.done).all()):
+            break
+    else:
+        raise RuntimeError("episodes did not finish")
+    ms = env.backend.numpy(env.makespan).astype(np.int64).reshape(P)
+    if return_solution:
+        return ms, env.backend.numpy(env.solution).astype(np.int64).reshape(P, J, M)
+    return ms
+
+
 DISPATCHING_RULES = {                                                     # dispatching.py:412-420
     "SPT": ShortestProcessingTime(),
     "FIFO": FirstInFirstOut(),
@@ -393,9 +561,11 @@ def compare_rules(env, rules: Optional[List[str]] = None, num_episodes: int = 10
             batch.reset()
             batch.zero_counters()
             for _ in range(64):
-                rule = get_rule(name)              # (a WeightedRule: its own row and its own exploration rate)
-                batch.rollout(device_kind(rule), n_iter=chunk, autoreset=False, weights=getattr(rule, "weights", None),
-                              explore=getattr(rule, "explore", EXPLORATION_PROBABILITY))
+                rule = get_rule(name)              # (a WeightedRule / KeyRule: its own row / table and its own exploration rate)
+                own = {"keys": rule._device_keys(env), "nope_key": rule.nope_key} if rule.kind == "keys" else \
+                      {"weights": getattr(rule, "weights", None)}
+                batch.rollout(device_kind(rule), n_iter=chunk, autoreset=False,
+                              explore=getattr(rule, "explore", EXPLORATION_PROBABILITY), **own)
                 if bool(batch.backend.numpy(batch.done).all()):
                     break
             else:

@@ -613,7 +613,7 @@ class BatchedJssEnv:
 
     # -- search: candidate moves scored by rule rollouts (jss_lookahead, include/jss_search.h) ----------------------------
     def lookahead(self, kind: Union[str, int] = "SPT", actions=None, parents=None, n_iter: Optional[int] = None,
-                  seed: Optional[int] = None, explore: float = 0.0, id_base: int = 0, weights=None):
+                  seed: Optional[int] = None, explore: float = 0.0, id_base: int = 0, weights=None, keys=None, nope_key=None):
         """Score candidate moves without cloning: candidate k starts from env ``parents[k]``, takes ``actions[k]`` (job, J =
         NOPE, -1 = none) and then follows the rule ``kind`` to the end of the episode, on the device, in registers; the batch
         is not touched.  Exactly what ``fork([parents[k]], env_id_base=id_base + k)``, ``step(actions[k])`` and
@@ -627,7 +627,8 @@ class BatchedJssEnv:
         ``(B, jmax + 1)`` (illegal and padded columns -1).  ``n_iter=None``: ``3 * jmax * mmax``, enough to finish any
         episode.  A batch dealt out by shape class is evaluated in one launch on the padded extents' kernel.
         ``weights`` (with ``kind="weighted"``): the continuation follows the caller's weighted rule (``jss_rule_lookahead``,
-        see ``policy``), candidate k with the row of ``parents[k]``."""
+        see ``policy``), candidate k with the row of ``parents[k]``.  ``keys`` / ``nope_key`` (with ``kind="keys"``): it follows
+        the caller's key tables (``jss_key_lookahead``), candidate k with the table of ``parents[k]``."""
         if not self._is_reset:
             raise RuntimeError("call reset() before lookahead()")
         self._no_open_session("lookahead")
@@ -638,7 +639,7 @@ class BatchedJssEnv:
             _abi.bind_search(be.lib)
         t = getattr(be, "torch", None)
         B, A = self.batch, self.jmax + 1
-        rule = self._rule_arg(kind, weights, "lookahead")
+        rule = self._rule_arg(kind, weights, "lookahead", keys, nope_key)
         k = None if rule else _abi.policy_code(kind)
         n_iter = 3 * self.jmax * self.mmax if n_iter is None else int(n_iter)
         with be.on_device():
@@ -662,10 +663,10 @@ class BatchedJssEnv:
             if n:
                 p = be.ptr
                 la = _abi.JssLookahead(n, p(par), p(act), int(id_base), p(makespan), p(steps), p(rnum))
-                call = be.lib.jss_rule_lookahead if rule else be.lib.jss_lookahead
+                call = getattr(be.lib, rule[2] + "_lookahead") if rule else be.lib.jss_lookahead
                 rc = call(C.byref(self._desc), C.byref(self._state), C.byref(la), C.byref(rule[0]) if rule else k,
                           self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter, be.stream())
-                _abi.check(be.lib, rc, "jss_rule_lookahead" if rule else "jss_lookahead")
+                _abi.check(be.lib, rc, rule[2] + "_lookahead" if rule else "jss_lookahead")
             # the return: reward numerators over the parent's max_time_op (0 where nothing was evaluated)
             if t is not None:
                 mto = self.env_const[:, _abi.C_MAX_TIME_OP].to(t.float64)[par.long().clamp(0, max(B - 1, 0))] if B else \
@@ -677,7 +678,8 @@ class BatchedJssEnv:
                 ret = np.where(mto > 0, rnum / np.maximum(mto, 1), 0.0).astype(np.float32)
         return makespan.reshape(shape), steps.reshape(shape), ret.reshape(shape)
 
-    def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None):
+    def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
+                   keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the
         rule to the end), and each env takes the action with the lowest makespan -- ties to the lowest index, -1 scores
         count as +inf.  An env none of whose actions can be scored (it is done) is left alone (``JSS_ACTION_SKIP``), or reset
@@ -685,7 +687,7 @@ class BatchedJssEnv:
         taken, ``info["scores"]`` the (B, jmax + 1) makespans."""
         be = self.backend
         t = getattr(be, "torch", None)
-        scores, _, _ = self.lookahead(kind, seed=seed, weights=weights)
+        scores, _, _ = self.lookahead(kind, seed=seed, weights=weights, keys=keys, nope_key=nope_key)
         none = _abi.ACTION_RESET if autoreset else _abi.ACTION_SKIP
         with be.on_device():
             if t is not None:
@@ -704,12 +706,21 @@ class BatchedJssEnv:
         """policy_code for the calls that know the stock rules only."""
         if kind == "weighted":
             raise NotImplementedError(f"{what} has no weighted-rule form: policy, rollout, lookahead and pilot_step take weights=")
+        if kind == "keys":
+            raise NotImplementedError(f"{what} has no key-table form: policy, rollout, lookahead and pilot_step take keys=")
         return _abi.policy_code(kind)
 
-    def _rule_arg(self, kind, weights, what):
-        """None for a stock ``kind``; for ``kind="weighted"`` the ``(JssRule, array kept alive)`` of ``weights``: an int32
-        tensor or array of shape (8,) -- one row for every env -- or (B, 8) -- env i uses row i --, on the host or on the env's
-        device.  Anything else raises ValueError."""
+    def _rule_arg(self, kind, weights, what, keys=None, nope_key=None):
+        """None for a stock ``kind``; for ``kind="weighted"`` the ``(JssRule, array kept alive, "jss_rule")`` of ``weights``: an
+        int32 tensor or array of shape (8,) -- one row for every env -- or (B, 8) -- env i uses row i --, on the host or on the
+        env's device; for ``kind="keys"`` the ``(JssKeys, array kept alive, "jss_key")`` of ``keys`` (``_keys_arg``).  The third
+        item is the prefix of the library's calls.  Anything else raises ValueError."""
+        if kind == "keys":
+            if weights is not None:
+                raise ValueError(f"{what}: weights= goes with kind='weighted'")
+            return self._keys_arg(keys, nope_key, what)
+        if keys is not None or nope_key is not None:
+            raise ValueError(f"{what}: keys= and nope_key= go with kind='keys'")
         if kind != "weighted":
             if weights is not None:
                 raise ValueError(f"{what}: weights= goes with kind='weighted'")
@@ -733,7 +744,35 @@ class BatchedJssEnv:
             w = np.array(w, copy=True)                                   # (as_device keeps one array alive: this one is ours)
         elif be.ptr(w) % 16:
             w = w.clone()                                                # (a view at an odd offset: rows are read 16 bytes at a time)
-        return _abi.JssRule(be.ptr(w), _abi.RW_N if len(shape) == 2 else 0), w
+        return _abi.JssRule(be.ptr(w), _abi.RW_N if len(shape) == 2 else 0), w, "jss_rule"
+
+    # -- per-operation priority keys (include/jss_keys.h) ---------------------------------------------------------------
+    def _keys_arg(self, keys, nope_key, what):
+        """The ``(JssKeys, array kept alive, "jss_key")`` of ``keys``: an int32 tensor or array of shape (jmax, mmax) -- one
+        table for every env -- or (B, jmax, mmax) -- env i uses table i --, on the host or on the env's device; ``nope_key``:
+        NOPE's key, None = INT32_MIN, NOPE only when no job is legal."""
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError(f"{what}: key tables do not run while a step session is open on the env")
+        be = self.backend
+        J, M = self.jmax, self.mmax
+        dt = getattr(keys, "dtype", None)
+        if dt is None or str(dt).split(".")[-1] != "int32":
+            raise ValueError(f"{what}: keys must be an int32 tensor or array of shape ({J}, {M}) or ({self.batch}, {J}, {M}) -- "
+                             "dispatching.keys_from_floats maps float priorities")
+        shape = tuple(keys.shape)
+        if shape != (J, M) and shape != (self.batch, J, M):
+            raise ValueError(f"{what}: keys must have shape ({J}, {M}) or ({self.batch}, {J}, {M}), got {shape}")
+        nope = _abi.KEY_NEVER_NOPE if nope_key is None else int(nope_key)
+        if not -2**31 <= nope < 2**31:
+            raise ValueError(f"{what}: nope_key must be in the int32 range")
+        if not hasattr(be.lib, "jss_key_policy"):
+            raise RuntimeError(f"{what}: the loaded library does not export the jss_key_* calls of include/jss_keys.h")
+        if be.lib.jss_key_policy.argtypes is None:                       # a library bound without include/jss_keys.h so far
+            _abi.bind_keys(be.lib)
+        k = be.as_device(keys, "int32")
+        if getattr(be, "torch", None) is None:
+            k = np.array(k, copy=True)                                   # (as_device keeps one array alive: this one is ours)
+        return _abi.JssKeys(be.ptr(k), J * M if len(shape) == 3 else 0, nope), k, "jss_key"
 
     # -- raw ABI handles (bench.py launches through these) -------------------------------
     @property
@@ -831,7 +870,7 @@ class BatchedJssEnv:
         return self._hole
 
     def policy(self, kind: Union[str, int] = "random", seed: Optional[int] = None, explore: float = 0.0,
-               cr_factor: Optional[float] = None, weights=None):
+               cr_factor: Optional[float] = None, weights=None, keys=None, nope_key=None):
         """Per-env action from the on-device selectors (random masked, FIFO, SPT, MWR, LWR, MOR, LOR, CR).
         Returns the env's own (B,) int32 action buffer (overwritten by the next policy() call).
         ``cr_factor``: CriticalRatio(due_date_factor=...) with ANY positive float (dispatching.py:337-360) -- the selector then
@@ -840,19 +879,23 @@ class BatchedJssEnv:
         ``kind="weighted"`` with ``weights``: the caller's rule (``jss_rule_policy``, include/jss_rules.h) -- the legal job
         with the largest integer score ``sum_f weights[f] * x_f(job)`` over SPT's, MWR's, MOR's, FIFO's ... quantities, NOPE by
         its bias ``weights[7]``; one int32 row of 8 for every env, or (B, 8): a population, env i with row i.  A batch dealt
-        out by shape class runs on the padded extents' kernel."""
+        out by shape class runs on the padded extents' kernel.
+        ``kind="keys"`` with ``keys``: the caller's priority per OPERATION (``jss_key_policy``, include/jss_keys.h) -- the legal
+        job whose current operation has the largest key, ``keys[job][ops the job has completed]``, the lowest index on ties;
+        NOPE, where it is legal, when ``nope_key`` exceeds that key (None: never while a job is legal); one int32 table
+        (jmax, mmax) for every env, or (B, jmax, mmax): a population of chromosomes, env i with table i."""
         if not self._is_reset:
             raise RuntimeError("call reset() before policy()")
         be = self.backend
-        rule = self._rule_arg(kind, weights, "policy")
+        rule = self._rule_arg(kind, weights, "policy", keys, nope_key)
         if rule:
             if cr_factor is not None:
                 raise ValueError("cr_factor is CriticalRatio's due-date factor: a positive float, with kind 'CR'")
             d, s, _ = self._refs()
             with be.on_device():
-                _abi.check(be.lib, be.lib.jss_rule_policy(d, s, C.byref(rule[0]), self.seed if seed is None else int(seed),
-                                                          int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()),
-                           "jss_rule_policy")
+                call = getattr(be.lib, rule[2] + "_policy")
+                _abi.check(be.lib, call(d, s, C.byref(rule[0]), self.seed if seed is None else int(seed),
+                                        int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()), rule[2] + "_policy")
             return self._actions_out
         k = _abi.policy_code(kind)
         if cr_factor is not None:
@@ -965,24 +1008,26 @@ class BatchedJssEnv:
         return info
 
     def rollout(self, kind: Union[str, int] = "random", n_iter: int = 1, seed: Optional[int] = None,
-                autoreset: bool = True, explore: float = 0.0, weights=None):
+                autoreset: bool = True, explore: float = 0.0, weights=None, keys=None, nope_key=None):
         """n_iter x (policy + step) per env in ONE launch (state stays in registers).  ``kind="weighted"`` with
         ``weights``: the caller's rule (``jss_rule_rollout``; see ``policy``) -- with one row per env, a population of rules
         plays its episodes in one launch.  On a batch of generated instances with ``fresh=True`` the weighted form takes
-        ``autoreset=False`` only, also for one iteration (the stock form regenerates the envs found done first)."""
+        ``autoreset=False`` only, also for one iteration (the stock form regenerates the envs found done first).
+        ``kind="keys"`` with ``keys`` / ``nope_key``: the caller's key tables (``jss_key_rollout``; see ``policy``), under the
+        same conditions -- with one table per env, a population of chromosomes is decoded in one launch."""
         if not self._is_reset:
             raise RuntimeError("call reset() before rollout()")
         be = self.backend
-        rule = self._rule_arg(kind, weights, "rollout")
+        rule = self._rule_arg(kind, weights, "rollout", keys, nope_key)
         if rule:
             flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
             d, s, o = self._refs()
             if autoreset and self.fresh:
-                self._refuse_fresh("rollout(kind='weighted', autoreset=True)")
+                self._refuse_fresh(f"rollout(kind='{kind}', autoreset=True)")
             with be.on_device():
-                rc = be.lib.jss_rule_rollout(d, s, o, C.byref(rule[0]), self.seed if seed is None else int(seed),
-                                             int(round(explore * 65536)), int(n_iter), flags, be.stream())
-                _abi.check(be.lib, rc, "jss_rule_rollout")
+                rc = getattr(be.lib, rule[2] + "_rollout")(d, s, o, C.byref(rule[0]), self.seed if seed is None else int(seed),
+                                                           int(round(explore * 65536)), int(n_iter), flags, be.stream())
+                _abi.check(be.lib, rc, rule[2] + "_rollout")
             return self._obs(), self.reward, self.done, False, {}
         k = _abi.policy_code(kind)
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0

@@ -344,7 +344,7 @@ class JssEnv(gymnasium_base("Env")):
         new.start_timestamp = self.start_timestamp
         return new
 
-    def _run_rule(self, kind, explore: float = 0.0, seed=None, weights=None):
+    def _run_rule(self, kind, explore: float = 0.0, seed=None, weights=None, keys=None, nope_key=None):
         """One whole episode of a dispatching rule, rule + step fused on the device (dispatching.py:55-75 with the
         exploration drawn from the counter RNG).  Returns (total reward, makespan) like ``run_episode``."""
         b = self._b
@@ -355,7 +355,7 @@ class JssEnv(gymnasium_base("Env")):
         self._alloc_log, self._alloc_log_ok = [], False      # the device picks the actions: no per-call log (next_jobs)
         chunk = self.jobs * self.machines + 16
         for _ in range(64):
-            b.rollout(kind, n_iter=chunk, autoreset=False, explore=explore, weights=weights)
+            b.rollout(kind, n_iter=chunk, autoreset=False, explore=explore, weights=weights, keys=keys, nope_key=nope_key)
             self._cache = None
             h = self._h()
             if h["done"]:
