@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
 
 ABI_VERSION = 14
 STATE_LAYOUT = 7     # version of the state tensors' layout (checkpoints): unchanged since ABI v7
@@ -244,6 +245,28 @@ def bind_keys(lib):
     lib.jss_key_lookahead.restype = C.c_int
     lib.jss_key_lookahead.argtypes = [D, S, C.POINTER(JssLookahead), K, C.c_uint64, C.c_uint32, C.c_int32, _p]
     return lib
+
+
+# The entry-point families behind a selector, by the prefix of their calls: jss_<verb> (the stock rules; include/jss_hip.h is
+# bound by `bind`, what may still be missing is the companion header of jss_lookahead), jss_rule_<verb>, jss_key_<verb>.
+# Per family: what its companion header declares, what attaches those prototypes, and the header's name.
+_FAMILIES = {"jss": (SEARCH_SYMBOLS, bind_search, "jss_search.h"), "jss_rule": (RULES_SYMBOLS, bind_rules, "jss_rules.h"),
+             "jss_key": (KEYS_SYMBOLS, bind_keys, "jss_keys.h")}
+
+
+def ensure_bound(lib, family: str, what: Optional[str] = None):
+    """``lib`` with the prototypes of ``family``'s companion header attached (now, unless they are already).  A library that
+    does not export every call of the header (a build of the same ABI version older than the header): None, and nothing is
+    attached, or -- given ``what``, the caller's name for its messages -- RuntimeError."""
+    symbols, binder, header = _FAMILIES[family]
+    first = getattr(lib, symbols[0], None)
+    if first is not None and first.argtypes is not None:                  # (attached earlier: every call is there)
+        return lib
+    if not all(hasattr(lib, name) for name in symbols):
+        if what is None:
+            return None
+        raise RuntimeError(f"{what}: the loaded library does not export the {family}_* calls of include/{header}")
+    return binder(lib)
 
 
 def check(lib, rc: int, what: str):

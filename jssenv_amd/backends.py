@@ -38,10 +38,8 @@ class HipBackend:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = _abi.bind_search(_abi.bind(C.CDLL(path)))
-        if all(hasattr(self.lib, name) for name in _abi.RULES_SYMBOLS):   # (a build of the v14 ABI older than include/jss_rules.h
-            _abi.bind_rules(self.lib)                                     #  still serves everything else: its first weighted call raises)
-        if all(hasattr(self.lib, name) for name in _abi.KEYS_SYMBOLS):    # (likewise for include/jss_keys.h)
-            _abi.bind_keys(self.lib)
+        for family in ("jss_rule", "jss_key"):       # (a build of the v14 ABI older than include/jss_rules.h or jss_keys.h still
+            _abi.ensure_bound(self.lib, family)      #  serves everything else: its first weighted or key call raises)
         if not self.lib.jss_backend().startswith(b"hip"):
             raise RuntimeError(f"{path} is not the HIP library ({self.lib.jss_backend()!r})")
         self._scalars = {}

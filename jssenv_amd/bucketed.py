@@ -31,7 +31,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .env import BatchedJssEnv
+from .env import BatchedJssEnv, stock_code
 from .instances import resolve_instance
 
 
@@ -41,14 +41,6 @@ def shape_class(jobs: int, machines: int) -> int:
     if jobs <= 32 and machines <= 32:
         return 1
     return 2 if jobs <= 64 else 3
-
-
-def _stock_kind(kind):
-    if kind == "weighted":
-        raise NotImplementedError("BucketedJssEnv knows the stock rules only: weighted rules run on BatchedJssEnv (weights=)")
-    if kind == "keys":
-        raise NotImplementedError("BucketedJssEnv knows the stock rules only: key tables run on BatchedJssEnv (keys=)")
-    return kind
 
 
 class BucketedJssEnv:
@@ -150,7 +142,7 @@ class BucketedJssEnv:
             return
         self._check_reset("rollout_steps")
         be = self._backend
-        k = _abi.policy_code(_stock_kind(kind))
+        k = stock_code(kind)
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         q16 = int(round(explore * 65536))
         with be.on_device():
@@ -176,7 +168,7 @@ class BucketedJssEnv:
         self._check_reset("policy")
         be = self._backend
         with be.on_device():
-            rc = be.lib.jss_multi_policy(self._n_sets, self._sets[0], self._sets[1], _abi.policy_code(_stock_kind(kind)), self._seed(seed),
+            rc = be.lib.jss_multi_policy(self._n_sets, self._sets[0], self._sets[1], stock_code(kind), self._seed(seed),
                                          int(round(explore * 65536)), self._policy_out, be.stream())
         _abi.check(be.lib, rc, "jss_multi_policy")
         return {k: b._actions_out for k, b in self._each()}

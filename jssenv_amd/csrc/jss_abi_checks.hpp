@@ -53,6 +53,38 @@ inline int check_kind(const JssDesc *d, int kind_arg, bool f64_ok = false) {
     return 0;
 }
 
+// a JssRule, where its call's namesake checks `kind`: the selector reads the remaining-work table whatever the weights are
+inline int check_rule(const JssDesc *d, const JssRule *rule) {
+    if (!rule || !rule->weights || !d->rem) return JSS_E_NULL;
+    if (reinterpret_cast<uintptr_t>(rule->weights) & 15) return JSS_E_SHAPE;      // rows are read four weights at a time
+    return rule->stride == 0 || rule->stride == JSS_RW_N ? 0 : JSS_E_SHAPE;
+}
+
+// a JssKeys, where its call's namesake checks `kind` (the selector reads no table of the batch's own: JssDesc.rem may be NULL)
+inline int check_keys(const JssDesc *d, const JssKeys *keys) {
+    if (!keys || !keys->keys) return JSS_E_NULL;
+    return keys->stride == 0 || keys->stride == d->jmax * d->mmax ? 0 : JSS_E_SHAPE;
+}
+
+// What picks the actions of a jss_policy / jss_rollout / jss_lookahead call and of their jss_rule_* (include/jss_rules.h) and
+// jss_key_* (include/jss_keys.h) namesakes: a stock rule's `kind`, the caller's weight rows or the caller's key tables.  The
+// three are one call each, checked, planned and launched by one path in either library.
+struct SelectorArg {
+    enum Which { kStock, kRule, kKeys } which;
+    int kind;                // kStock
+    const JssRule *rule;     // kRule (may be NULL: check_rule says so)
+    const JssKeys *keys;     // kKeys (likewise)
+};
+inline SelectorArg stock_selector(int kind) { return {SelectorArg::kStock, kind, nullptr, nullptr}; }
+inline SelectorArg rule_selector(const JssRule *rule) { return {SelectorArg::kRule, 0, rule, nullptr}; }
+inline SelectorArg keys_selector(const JssKeys *keys) { return {SelectorArg::kKeys, 0, nullptr, keys}; }
+
+// f64_ok: as for check_kind (the caller's selectors have no such form)
+inline int check_selector(const JssDesc *d, const SelectorArg &sel, bool f64_ok = false) {
+    return sel.which == SelectorArg::kRule ? check_rule(d, sel.rule) : sel.which == SelectorArg::kKeys ? check_keys(d, sel.keys)
+                                                                                                      : check_kind(d, sel.kind, f64_ok);
+}
+
 // a JssLogits against its set's description
 inline int check_logits(const JssDesc *d, const JssLogits *lg) {
     if (!lg || !lg->logits || !lg->action) return JSS_E_NULL;
@@ -102,17 +134,19 @@ inline int check_step_logits(const JssDesc *d, const JssState *s, const JssLogit
     return rc ? rc : check_logits(d, lg);
 }
 
-inline int check_policy(const JssDesc *d, const JssState *s, int kind, const int32_t *actions) {
+// jss_policy, jss_rule_policy, jss_key_policy
+inline int check_policy(const JssDesc *d, const JssState *s, const SelectorArg &sel, const int32_t *actions) {
     const int rc = check_args(d, s, nullptr, false);
     if (rc) return rc;
     if (!actions) return JSS_E_NULL;
-    return check_kind(d, kind, true);
+    return check_selector(d, sel, true);
 }
 
-inline int check_rollout(const JssDesc *d, const JssState *s, const JssOut *o, int kind, int32_t n_iter) {
+// jss_rollout, jss_rule_rollout, jss_key_rollout
+inline int check_rollout(const JssDesc *d, const JssState *s, const JssOut *o, const SelectorArg &sel, int32_t n_iter) {
     int rc = check_args(d, s, o, true);
     if (rc) return rc;
-    if ((rc = check_kind(d, kind))) return rc;
+    if ((rc = check_selector(d, sel))) return rc;
     return n_iter < 0 ? JSS_E_SHAPE : 0;
 }
 
@@ -282,76 +316,15 @@ inline int check_clone(const JssDesc *dd, const JssState *ds, const JssOut *dout
 }
 
 // ---- search (include/jss_search.h) ---------------------------------------------------------------------------------
-// jss_lookahead: the batch as jss_rollout checks it, without a JssOut (nothing of the batch is written); the fused rollouts'
-// kinds (no JSS_POLICY_CR_F64)
-inline int check_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, int kind, int32_t n_iter) {
+// jss_lookahead, jss_rule_lookahead, jss_key_lookahead: the batch as jss_rollout checks it, without a JssOut (nothing of the
+// batch is written); the fused rollouts' kinds (no JSS_POLICY_CR_F64)
+inline int check_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, const SelectorArg &sel, int32_t n_iter) {
     if (!d || !s || !la) return JSS_E_NULL;
     int rc = check_args(d, s, nullptr, false);
     if (rc) return rc;
     if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
     if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
-    return check_kind(d, kind);
-}
-
-// ---- caller-weighted rules (include/jss_rules.h) -------------------------------------------------------------------
-// a JssRule, where its call's namesake checks `kind`: the selector reads the remaining-work table whatever the weights are
-inline int check_rule(const JssDesc *d, const JssRule *rule) {
-    if (!rule || !rule->weights || !d->rem) return JSS_E_NULL;
-    if (reinterpret_cast<uintptr_t>(rule->weights) & 15) return JSS_E_SHAPE;      // rows are read four weights at a time
-    return rule->stride == 0 || rule->stride == JSS_RW_N ? 0 : JSS_E_SHAPE;
-}
-
-inline int check_rule_policy(const JssDesc *d, const JssState *s, const JssRule *rule, const int32_t *actions) {
-    const int rc = check_args(d, s, nullptr, false);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
-    return check_rule(d, rule);
-}
-
-inline int check_rule_rollout(const JssDesc *d, const JssState *s, const JssOut *o, const JssRule *rule, int32_t n_iter) {
-    int rc = check_args(d, s, o, true);
-    if (rc) return rc;
-    if ((rc = check_rule(d, rule))) return rc;
-    return n_iter < 0 ? JSS_E_SHAPE : 0;
-}
-
-inline int check_rule_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, const JssRule *rule, int32_t n_iter) {
-    if (!d || !s || !la) return JSS_E_NULL;
-    int rc = check_args(d, s, nullptr, false);
-    if (rc) return rc;
-    if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
-    if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
-    return check_rule(d, rule);
-}
-
-// ---- per-operation priority keys (include/jss_keys.h) ----------------------------------------------------------------
-// a JssKeys, where its call's namesake checks `kind` (the selector reads no table of the batch's own: JssDesc.rem may be NULL)
-inline int check_keys(const JssDesc *d, const JssKeys *keys) {
-    if (!keys || !keys->keys) return JSS_E_NULL;
-    return keys->stride == 0 || keys->stride == d->jmax * d->mmax ? 0 : JSS_E_SHAPE;
-}
-
-inline int check_key_policy(const JssDesc *d, const JssState *s, const JssKeys *keys, const int32_t *actions) {
-    const int rc = check_args(d, s, nullptr, false);
-    if (rc) return rc;
-    if (!actions) return JSS_E_NULL;
-    return check_keys(d, keys);
-}
-
-inline int check_key_rollout(const JssDesc *d, const JssState *s, const JssOut *o, const JssKeys *keys, int32_t n_iter) {
-    int rc = check_args(d, s, o, true);
-    if (rc) return rc;
-    if ((rc = check_keys(d, keys))) return rc;
-    return n_iter < 0 ? JSS_E_SHAPE : 0;
-}
-
-inline int check_key_lookahead(const JssDesc *d, const JssState *s, const JssLookahead *la, const JssKeys *keys, int32_t n_iter) {
-    if (!d || !s || !la) return JSS_E_NULL;
-    int rc = check_args(d, s, nullptr, false);
-    if (rc) return rc;
-    if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
-    if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
-    return check_keys(d, keys);
+    return check_selector(d, sel);
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

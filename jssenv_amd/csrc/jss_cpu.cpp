@@ -933,6 +933,48 @@ void generate_env(const JssDesc &d, const JssState *s, const JssGen &g, int b) {
     rec[JSS_I_RCP_MACHINES] = rcp_bits(M);
 }
 
+// ---- policy, rollout, lookahead: ONE path each for the stock rules (jss_*), the caller's weighted rules (jss_rule_*,
+// include/jss_rules.h) and the caller's key tables (jss_key_*, include/jss_keys.h) ------------------------------------------
+// The selector into the Call: a stock rule's `kind` as it came; the caller's selectors as kinds of their own with their struct
+void apply(Call &c, const SelectorArg &sel) {
+    if (sel.which == SelectorArg::kRule) {
+        c.kind = kKindWeighted; c.rule = *sel.rule;
+    } else if (sel.which == SelectorArg::kKeys) {
+        c.kind = kKindKeys; c.keys = *sel.keys;
+    } else {
+        c.kind = sel.kind;
+    }
+}
+
+int policy_call(const JssDesc *desc, const JssState *state, const SelectorArg &sel, uint64_t seed, uint32_t explore_q16,
+                int32_t *actions) {
+    if (const int rc = check_policy(desc, state, sel, actions)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.seed = seed; c.explore_q16 = explore_q16;
+    apply(c, sel);
+    return run(c, kPolicy);
+}
+
+int rollout_call(const JssDesc *desc, const JssState *state, const JssOut *out, const SelectorArg &sel, uint64_t seed,
+                 uint32_t explore_q16, int32_t n_iter, int32_t flags) {
+    if (const int rc = check_rollout(desc, state, out, sel, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = *out; c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter; c.flags = flags;
+    apply(c, sel);
+    return run(c, kRollout);
+}
+
+int lookahead_call(const JssDesc *desc, const JssState *state, const JssLookahead *la, const SelectorArg &sel, uint64_t seed,
+                   uint32_t explore_q16, int32_t n_iter) {
+    if (const int rc = check_lookahead(desc, state, la, sel, n_iter)) return rc;
+    Call c;
+    c.d = *desc; c.s = *state; c.o = JssOut(); c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter;
+    apply(c, sel);
+    const JssLookahead l = *la;
+    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -991,19 +1033,12 @@ int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which
 
 int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t seed, uint32_t explore_q16, int32_t *actions,
                void *) {
-    if (const int rc = check_policy(desc, state, kind, actions)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16;
-    return run(c, kPolicy);
+    return policy_call(desc, state, stock_selector(kind), seed, explore_q16, actions);
 }
 
 int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed, uint32_t explore_q16,
                 int32_t n_iter, int32_t flags, void *) {
-    if (const int rc = check_rollout(desc, state, out, kind, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = *out; c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16;
-    c.n_iter = n_iter; c.flags = flags;
-    return run(c, kRollout);
+    return rollout_call(desc, state, out, stock_selector(kind), seed, explore_q16, n_iter, flags);
 }
 
 int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, int kind,
@@ -1187,74 +1222,40 @@ int jss_generate(const JssDesc *desc, const JssState *state, const JssGen *gen, 
     return 0;
 }
 
+// include/jss_search.h, include/jss_rules.h, include/jss_keys.h: the companions of jss_policy and jss_rollout above
 int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, int kind, uint64_t seed,
                   uint32_t explore_q16, int32_t n_iter, void *) {
-    if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kind; c.seed = seed; c.explore_q16 = explore_q16; c.n_iter = n_iter;
-    const JssLookahead l = *la;
-    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
-    return 0;
+    return lookahead_call(desc, state, la, stock_selector(kind), seed, explore_q16, n_iter);
 }
 
-// include/jss_rules.h: the namesakes' calls with Call.kind = kKindWeighted and the weight rows
 int jss_rule_policy(const JssDesc *desc, const JssState *state, const JssRule *rule, uint64_t seed, uint32_t explore_q16,
                     int32_t *actions, void *) {
-    if (const int rc = check_rule_policy(desc, state, rule, actions)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kKindWeighted; c.rule = *rule; c.seed = seed;
-    c.explore_q16 = explore_q16;
-    return run(c, kPolicy);
+    return policy_call(desc, state, rule_selector(rule), seed, explore_q16, actions);
 }
 
 int jss_rule_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssRule *rule, uint64_t seed,
                      uint32_t explore_q16, int32_t n_iter, int32_t flags, void *) {
-    if (const int rc = check_rule_rollout(desc, state, out, rule, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = *out; c.kind = kKindWeighted; c.rule = *rule; c.seed = seed; c.explore_q16 = explore_q16;
-    c.n_iter = n_iter; c.flags = flags;
-    return run(c, kRollout);
+    return rollout_call(desc, state, out, rule_selector(rule), seed, explore_q16, n_iter, flags);
 }
 
 int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssRule *rule,
                        uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *) {
-    if (const int rc = check_rule_lookahead(desc, state, la, rule, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kKindWeighted; c.rule = *rule; c.seed = seed; c.explore_q16 = explore_q16;
-    c.n_iter = n_iter;
-    const JssLookahead l = *la;
-    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
-    return 0;
+    return lookahead_call(desc, state, la, rule_selector(rule), seed, explore_q16, n_iter);
 }
 
-// include/jss_keys.h: the namesakes' calls with Call.kind = kKindKeys and the key tables
 int jss_key_policy(const JssDesc *desc, const JssState *state, const JssKeys *keys, uint64_t seed, uint32_t explore_q16,
                    int32_t *actions, void *) {
-    if (const int rc = check_key_policy(desc, state, keys, actions)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.actions_out = actions; c.kind = kKindKeys; c.keys = *keys; c.seed = seed;
-    c.explore_q16 = explore_q16;
-    return run(c, kPolicy);
+    return policy_call(desc, state, keys_selector(keys), seed, explore_q16, actions);
 }
 
 int jss_key_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssKeys *keys, uint64_t seed,
                     uint32_t explore_q16, int32_t n_iter, int32_t flags, void *) {
-    if (const int rc = check_key_rollout(desc, state, out, keys, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = *out; c.kind = kKindKeys; c.keys = *keys; c.seed = seed; c.explore_q16 = explore_q16;
-    c.n_iter = n_iter; c.flags = flags;
-    return run(c, kRollout);
+    return rollout_call(desc, state, out, keys_selector(keys), seed, explore_q16, n_iter, flags);
 }
 
 int jss_key_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssKeys *keys,
                       uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *) {
-    if (const int rc = check_key_lookahead(desc, state, la, keys, n_iter)) return rc;
-    Call c;
-    c.d = *desc; c.s = *state; c.o = JssOut(); c.kind = kKindKeys; c.keys = *keys; c.seed = seed; c.explore_q16 = explore_q16;
-    c.n_iter = n_iter;
-    const JssLookahead l = *la;
-    parallel_for<true>(l.n, c.d.threads, [&](int k) { lookahead_one(c, l, k); });
-    return 0;
+    return lookahead_call(desc, state, la, keys_selector(keys), seed, explore_q16, n_iter);
 }
 
 int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_out, const JssCloneDst *dst_tables,

@@ -560,7 +560,7 @@ int launch_multi(Params *ps, int n, int n_steps, int n_sub, void *const *streams
     });
 }
 
-// kLookahead over the candidates p.la of the batch p describes (jss_lookahead, jss_rule_lookahead)
+// kLookahead over the candidates p.la of the batch p describes (lookahead_call)
 int launch_lookahead(Params &p, void *stream) {
     // (the widest per-env rows a packed kernel offsets: job records, <= jmax x 32 bytes, and the 48-byte constants record)
     if ((unsigned long long)p.d.batch * ((unsigned long long)p.d.jmax * JSS_NF * 4 + JSS_NC * 4) >= (1ull << 32))
@@ -570,6 +570,20 @@ int launch_lookahead(Params &p, void *stream) {
     const int blocks = (int)(((long long)p.la.n + lp.envs_per_block - 1) / lp.envs_per_block);
     hipLaunchKernelGGL(lp.fn, dim3(blocks), dim3(kBlock), lp.shmem, reinterpret_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+// ---- policy, rollout, lookahead: ONE path each for the stock rules (jss_*), the caller's weighted rules (jss_rule_*,
+// include/jss_rules.h) and the caller's key tables (jss_key_*, include/jss_keys.h) ------------------------------------------
+// The selector into Params: a stock rule's `kind` as it came; the caller's selectors as kinds of their own, which are no
+// JSS_POLICY_* codes, with the rule or the keys in the 16-byte slot the two share.
+void apply(Params &p, const SelectorArg &sel) {
+    if (sel.which == SelectorArg::kRule) {
+        p.kind = kKindWeighted; p.rule = *sel.rule;
+    } else if (sel.which == SelectorArg::kKeys) {
+        p.kind = kKindKeys; p.keys = *sel.keys;
+    } else {
+        p.kind = sel.kind;
+    }
 }
 
 }  // namespace
@@ -643,21 +657,50 @@ int jss_advance(const JssDesc *desc, const JssState *state, const uint8_t *which
     return launch<kAdvance>(p, stream);
 }
 
+// The three call shapes.  (They stand here, not with `apply`: the kernel instantiations are emitted in the order in which this
+// file first names them, and the code object is held byte for byte to the one that jss_policy and jss_rollout gave here.)
+static int policy_call(const JssDesc *desc, const JssState *state, const SelectorArg &sel, uint64_t seed, uint32_t explore_q16,
+                       int32_t *actions, void *stream) {
+    if (const int rc = check_policy(desc, state, sel, actions)) return rc;
+    Params p = params_of(desc, state, nullptr);
+    apply(p, sel);
+    p.actions_out = actions; p.seed = seed; p.explore_q16 = explore_q16;
+    return launch<kPolicy>(p, stream);
+}
+
+static int rollout_call(const JssDesc *desc, const JssState *state, const JssOut *out, const SelectorArg &sel, uint64_t seed,
+                        uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
+    if (const int rc = check_rollout(desc, state, out, sel, n_iter)) return rc;
+    Params p = params_of(desc, state, out);
+    apply(p, sel);
+    p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter; p.flags = flags;
+    // One iteration of a stock rule runs on the one-step kernels.  The caller's selectors plan kRollout whatever n_iter is:
+    // kRollout1 (and kStep) do not carry them.
+    return n_iter == 1 && sel.which == SelectorArg::kStock ? launch<kRollout1>(p, stream) : launch<kRollout>(p, stream);
+}
+
+// Candidate moves scored by rule rollouts (include/jss_search.h): kLookahead, a group (packed) or a wavefront per candidate,
+// the kernel flavour and table layout of the batch as for jss_rollout.  The packed kernels address a parent's rows by a 32-bit
+// lane offset from the start of the batch's tensors; a batch too large for that runs on the one-wavefront-per-env kernels,
+// which address an env by a wave-uniform 64-bit base.
+static int lookahead_call(const JssDesc *desc, const JssState *state, const JssLookahead *la, const SelectorArg &sel,
+                          uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *stream) {
+    if (const int rc = check_lookahead(desc, state, la, sel, n_iter)) return rc;
+    if (la->n == 0) return 0;                         // no candidate: nothing is planned (no JSS_E_LDS), nothing is launched
+    Params p = params_of(desc, state, nullptr);
+    apply(p, sel);
+    p.la = *la; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
+    return launch_lookahead(p, stream);
+}
+
 int jss_policy(const JssDesc *desc, const JssState *state, int kind, uint64_t seed, uint32_t explore_q16,
                int32_t *actions, void *stream) {
-    if (const int rc = check_policy(desc, state, kind, actions)) return rc;
-    Params p = params_of(desc, state, nullptr);
-    p.actions_out = actions; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
-    return launch<kPolicy>(p, stream);
+    return policy_call(desc, state, stock_selector(kind), seed, explore_q16, actions, stream);
 }
 
 int jss_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, int kind, uint64_t seed,
                 uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
-    if (const int rc = check_rollout(desc, state, out, kind, n_iter)) return rc;
-    Params p = params_of(desc, state, out);
-    p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16;
-    p.n_iter = n_iter; p.flags = flags;
-    return n_iter == 1 ? launch<kRollout1>(p, stream) : launch<kRollout>(p, stream);
+    return rollout_call(desc, state, out, stock_selector(kind), seed, explore_q16, n_iter, flags, stream);
 }
 
 int jss_trajectory(const JssDesc *desc, const JssState *state, const JssOut *out, const JssTraj *traj, int kind,
@@ -940,73 +983,40 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
     return (int)hipGetLastError();
 }
 
-// Candidate moves scored by rule rollouts (include/jss_search.h): kLookahead, a group (packed) or a wavefront per candidate,
-// the kernel flavour and table layout of the batch as for jss_rollout.  The packed kernels address a parent's rows by a 32-bit
-// lane offset from the start of the batch's tensors; a batch too large for that runs on the one-wavefront-per-env kernels,
-// which address an env by a wave-uniform 64-bit base.
+// include/jss_search.h, include/jss_rules.h, include/jss_keys.h: the companions of jss_policy and jss_rollout above
 int jss_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, int kind, uint64_t seed,
                   uint32_t explore_q16, int32_t n_iter, void *stream) {
-    if (const int rc = check_lookahead(desc, state, la, kind, n_iter)) return rc;
-    if (la->n == 0) return 0;
-    Params p = params_of(desc, state, nullptr);
-    p.la = *la; p.kind = kind; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
-    return launch_lookahead(p, stream);
+    return lookahead_call(desc, state, la, stock_selector(kind), seed, explore_q16, n_iter, stream);
 }
 
-// Caller-weighted rules (include/jss_rules.h): the namesakes' launches with Params.kind = kKindWeighted and the weight rows.
-// jss_rule_rollout plans kRollout whatever n_iter is: the one-step kernels (kRollout1) do not carry the weighted selector.
 int jss_rule_policy(const JssDesc *desc, const JssState *state, const JssRule *rule, uint64_t seed, uint32_t explore_q16,
                     int32_t *actions, void *stream) {
-    if (const int rc = check_rule_policy(desc, state, rule, actions)) return rc;
-    Params p = params_of(desc, state, nullptr);
-    p.actions_out = actions; p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16;
-    return launch<kPolicy>(p, stream);
+    return policy_call(desc, state, rule_selector(rule), seed, explore_q16, actions, stream);
 }
 
 int jss_rule_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssRule *rule, uint64_t seed,
                      uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
-    if (const int rc = check_rule_rollout(desc, state, out, rule, n_iter)) return rc;
-    Params p = params_of(desc, state, out);
-    p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16;
-    p.n_iter = n_iter; p.flags = flags;
-    return launch<kRollout>(p, stream);
+    return rollout_call(desc, state, out, rule_selector(rule), seed, explore_q16, n_iter, flags, stream);
 }
 
 int jss_rule_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssRule *rule,
                        uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *stream) {
-    if (const int rc = check_rule_lookahead(desc, state, la, rule, n_iter)) return rc;
-    if (la->n == 0) return 0;
-    Params p = params_of(desc, state, nullptr);
-    p.la = *la; p.kind = kKindWeighted; p.rule = *rule; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
-    return launch_lookahead(p, stream);
+    return lookahead_call(desc, state, la, rule_selector(rule), seed, explore_q16, n_iter, stream);
 }
 
-// Per-operation priority keys (include/jss_keys.h): the same launches with Params.kind = kKindKeys and the key tables, in the
-// kernels that carry the weighted selector.  jss_key_rollout plans kRollout whatever n_iter is, as jss_rule_rollout does.
 int jss_key_policy(const JssDesc *desc, const JssState *state, const JssKeys *keys, uint64_t seed, uint32_t explore_q16,
                    int32_t *actions, void *stream) {
-    if (const int rc = check_key_policy(desc, state, keys, actions)) return rc;
-    Params p = params_of(desc, state, nullptr);
-    p.actions_out = actions; p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16;
-    return launch<kPolicy>(p, stream);
+    return policy_call(desc, state, keys_selector(keys), seed, explore_q16, actions, stream);
 }
 
 int jss_key_rollout(const JssDesc *desc, const JssState *state, const JssOut *out, const JssKeys *keys, uint64_t seed,
                     uint32_t explore_q16, int32_t n_iter, int32_t flags, void *stream) {
-    if (const int rc = check_key_rollout(desc, state, out, keys, n_iter)) return rc;
-    Params p = params_of(desc, state, out);
-    p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16;
-    p.n_iter = n_iter; p.flags = flags;
-    return launch<kRollout>(p, stream);
+    return rollout_call(desc, state, out, keys_selector(keys), seed, explore_q16, n_iter, flags, stream);
 }
 
 int jss_key_lookahead(const JssDesc *desc, const JssState *state, const JssLookahead *la, const JssKeys *keys,
                       uint64_t seed, uint32_t explore_q16, int32_t n_iter, void *stream) {
-    if (const int rc = check_key_lookahead(desc, state, la, keys, n_iter)) return rc;
-    if (la->n == 0) return 0;
-    Params p = params_of(desc, state, nullptr);
-    p.la = *la; p.kind = kKindKeys; p.keys = *keys; p.seed = seed; p.explore_q16 = explore_q16; p.n_iter = n_iter;
-    return launch_lookahead(p, stream);
+    return lookahead_call(desc, state, la, keys_selector(keys), seed, explore_q16, n_iter, stream);
 }
 
 }  // extern "C"

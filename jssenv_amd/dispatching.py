@@ -320,7 +320,7 @@ def evaluate_weights(instances, weights, device=None, explore: float = 0.0, seed
     Every call builds its batch anew (allocation, upload of the instances, reset) and copies the makespans back: a loop over
     generations that wants neither keeps one ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and
     ``rollout("weighted", weights=w, autoreset=False)`` on it with ``w`` on the device -- the two lines this function ends in."""
-    from .env import BatchedJssEnv
+    from .env import BatchedJssEnv, play_to_end
     from .instances import Instance, builtin_instance
     one = isinstance(instances, (str, Instance))
     insts = [instances] if one else list(instances)
@@ -341,13 +341,7 @@ def evaluate_weights(instances, weights, device=None, explore: float = 0.0, seed
     if hasattr(rows, "repeat_interleave") and getattr(env.backend, "torch", None) is None:
         rows = rows.detach().cpu().numpy()                                # a tensor, and the host twin's NumPy memory
     env.reset()
-    chunk = env.jmax * env.mmax + 16
-    for _ in range(64):
-        env.rollout("weighted", n_iter=chunk, autoreset=False, explore=explore, weights=rows)
-        if bool(env.backend.numpy(env.done).all()):
-            break
-    else:
-        raise RuntimeError("episodes did not finish")
+    play_to_end(env, "weighted", explore, weights=rows)
     return env.backend.numpy(env.makespan).astype(np.int64).reshape(P, N)
 
 
@@ -491,7 +485,7 @@ def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, e
 
     Every call builds its batch anew, as ``evaluate_weights`` does: a loop over generations keeps one
     ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and ``rollout("keys", keys=k, autoreset=False)`` on it."""
-    from .env import BatchedJssEnv
+    from .env import BatchedJssEnv, play_to_end
     inst = _instance_of(instance)
     J, M = inst.jobs, inst.machines
     k = keys if hasattr(keys, "is_floating_point") else np.ascontiguousarray(np.asarray(keys))
@@ -506,13 +500,7 @@ def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, e
     if hasattr(k, "is_floating_point") and getattr(env.backend, "torch", None) is None:
         k = k.detach().cpu().numpy()                                      # a tensor, and the host twin's NumPy memory
     env.reset()
-    chunk = J * M + 16
-    for _ in range(64):
-        env.rollout("keys", n_iter=chunk, autoreset=False, explore=explore, keys=k, nope_key=nope_key)
-        if bool(env.backend.numpy(env.done).all()):
-            break
-    else:
-        raise RuntimeError("episodes did not finish")
+    play_to_end(env, "keys", explore, keys=k, nope_key=nope_key)
     ms = env.backend.numpy(env.makespan).astype(np.int64).reshape(P)
     if return_solution:
         return ms, env.backend.numpy(env.solution).astype(np.int64).reshape(P, J, M)
@@ -550,26 +538,19 @@ def compare_rules(env, rules: Optional[List[str]] = None, num_episodes: int = 10
     on_device = hasattr(env, "_b") and all(get_rule(n).kind is not None and _device_rule_ok(get_rule(n)) for n in names)
     results = {}
     if on_device and num_episodes > 0:
-        from .env import BatchedJssEnv
+        from .env import BatchedJssEnv, play_to_end
         base = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         inst = env.instance
         batch = BatchedJssEnv([inst], batch=int(num_episodes), seed=base, _backend=env._b.backend)
-        # an episode is J * M allocations plus its NOPEs; chunks of that size until every env reports done
-        chunk = inst.jobs * inst.machines + 16
         for k, name in enumerate(names):
             batch.seed = base + 7919 * k
             batch.reset()
             batch.zero_counters()
-            for _ in range(64):
-                rule = get_rule(name)              # (a WeightedRule / KeyRule: its own row / table and its own exploration rate)
-                own = {"keys": rule._device_keys(env), "nope_key": rule.nope_key} if rule.kind == "keys" else \
-                      {"weights": getattr(rule, "weights", None)}
-                batch.rollout(device_kind(rule), n_iter=chunk, autoreset=False,
-                              explore=getattr(rule, "explore", EXPLORATION_PROBABILITY), **own)
-                if bool(batch.backend.numpy(batch.done).all()):
-                    break
-            else:
-                raise RuntimeError(f"rule {name}: episodes did not finish")
+            rule = get_rule(name)                  # (a WeightedRule / KeyRule: its own row / table and its own exploration rate)
+            own = {"keys": rule._device_keys(env), "nope_key": rule.nope_key} if rule.kind == "keys" else \
+                  {"weights": getattr(rule, "weights", None)}
+            play_to_end(batch, device_kind(rule), getattr(rule, "explore", EXPLORATION_PROBABILITY),
+                        what=f"rule {name}: episodes", **own)
             cnt = batch.backend.numpy(batch.counters)
             results[name] = {"avg_reward": float(cnt[:, 3].sum()) / inst.max_time_op / num_episodes,
                              "avg_makespan": float(batch.backend.numpy(batch.makespan).sum()) / num_episodes}

@@ -18,6 +18,51 @@ from .backends import _NULL_CTX, CpuBackend, HipBackend, _carve_numpy, make_back
 from .instances import Instance, PackedBatch, MAX_DURATION, OP_MACHINE_SHIFT, pack_batch, resolve_instance
 
 
+class _Selector:
+    """What picks the actions of a policy / rollout / lookahead call, as the C ABI takes it: ``arg`` -- a stock rule's ``kind``
+    code, or ``byref`` of the caller's JssRule / JssKeys --, ``keep`` -- the array behind that struct, alive as long as this
+    object --, ``family`` -- the prefix of the entry points that take such an argument (jss, jss_rule, jss_key) -- and ``stock``."""
+    __slots__ = ("arg", "keep", "family", "stock")
+
+    def __init__(self, arg, keep=None, family="jss"):
+        self.stock = family == "jss"
+        self.arg, self.keep, self.family = arg if self.stock else C.byref(arg), (arg, keep), family
+
+    def call(self, lib, verb, head, *tail):
+        """<family>_<verb>(*head, the selector, *tail); RuntimeError naming the entry point unless it returns 0"""
+        name = self.family + "_" + verb
+        rc = getattr(lib, name)(*head, self.arg, *tail)
+        if rc:
+            _abi.check(lib, rc, name)
+
+
+_STOCK = {}          # kind -> the _Selector of a stock rule (they hold nothing of a call's own)
+
+
+def stock_code(kind, what=None):
+    """``_abi.policy_code`` for the calls that know the stock rules only: ``what`` names the BatchedJssEnv method, None stands
+    for BucketedJssEnv."""
+    if kind == "weighted":
+        raise NotImplementedError("BucketedJssEnv knows the stock rules only: weighted rules run on BatchedJssEnv (weights=)" if what is None
+                                  else f"{what} has no weighted-rule form: policy, rollout, lookahead and pilot_step take weights=")
+    if kind == "keys":
+        raise NotImplementedError("BucketedJssEnv knows the stock rules only: key tables run on BatchedJssEnv (keys=)" if what is None
+                                  else f"{what} has no key-table form: policy, rollout, lookahead and pilot_step take keys=")
+    return _abi.policy_code(kind)
+
+
+def play_to_end(env, kind, explore, done=None, what="episodes", **selector):
+    """Plays the (reset) envs of ``env`` to the end of their episodes with the rule ``kind`` (``selector``: its ``weights=`` /
+    ``keys=`` / ``nope_key=``): an episode is J * M allocations plus its NOPEs, so rollouts of that many steps, without
+    autoreset, until ``done()`` says that every env has finished -- by default, from ``env.done``."""
+    done = done or (lambda: bool(env.backend.numpy(env.done).all()))
+    for _ in range(64):
+        env.rollout(kind, n_iter=env.jmax * env.mmax + 16, autoreset=False, explore=explore, **selector)
+        if done():
+            return
+    raise RuntimeError(f"{what} did not finish")
+
+
 class BatchedJssEnv:
     """B independent job-shop envs on one GPU.
 
@@ -635,12 +680,10 @@ class BatchedJssEnv:
         if (actions is None) != (parents is None):
             raise ValueError("lookahead: give both parents and actions, or neither (every action of every env)")
         be = self.backend
-        if be.lib.jss_lookahead.argtypes is None:              # a library bound by _abi.bind alone (test backends)
-            _abi.bind_search(be.lib)
+        _abi.ensure_bound(be.lib, "jss")                       # (a library bound by _abi.bind alone: test backends)
         t = getattr(be, "torch", None)
         B, A = self.batch, self.jmax + 1
-        rule = self._rule_arg(kind, weights, "lookahead", keys, nope_key)
-        k = None if rule else _abi.policy_code(kind)
+        sel = self._selector(kind, "lookahead", weights, keys, nope_key)
         n_iter = 3 * self.jmax * self.mmax if n_iter is None else int(n_iter)
         with be.on_device():
             if parents is None:
@@ -663,10 +706,8 @@ class BatchedJssEnv:
             if n:
                 p = be.ptr
                 la = _abi.JssLookahead(n, p(par), p(act), int(id_base), p(makespan), p(steps), p(rnum))
-                call = getattr(be.lib, rule[2] + "_lookahead") if rule else be.lib.jss_lookahead
-                rc = call(C.byref(self._desc), C.byref(self._state), C.byref(la), C.byref(rule[0]) if rule else k,
-                          self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter, be.stream())
-                _abi.check(be.lib, rc, rule[2] + "_lookahead" if rule else "jss_lookahead")
+                sel.call(be.lib, "lookahead", (C.byref(self._desc), C.byref(self._state), C.byref(la)),
+                         self.seed if seed is None else int(seed), int(round(explore * 65536)), n_iter, be.stream())
             # the return: reward numerators over the parent's max_time_op (0 where nothing was evaluated)
             if t is not None:
                 mto = self.env_const[:, _abi.C_MAX_TIME_OP].to(t.float64)[par.long().clamp(0, max(B - 1, 0))] if B else \
@@ -701,78 +742,48 @@ class BatchedJssEnv:
         obs, reward, done, truncated, _ = self.step(action)
         return obs, reward, done, truncated, {"action": action, "scores": scores}
 
-    # -- caller-weighted rules (include/jss_rules.h) --------------------------------------------------------------------
-    def _stock_code(self, kind, what):
-        """policy_code for the calls that know the stock rules only."""
-        if kind == "weighted":
-            raise NotImplementedError(f"{what} has no weighted-rule form: policy, rollout, lookahead and pilot_step take weights=")
-        if kind == "keys":
-            raise NotImplementedError(f"{what} has no key-table form: policy, rollout, lookahead and pilot_step take keys=")
-        return _abi.policy_code(kind)
-
-    def _rule_arg(self, kind, weights, what, keys=None, nope_key=None):
-        """None for a stock ``kind``; for ``kind="weighted"`` the ``(JssRule, array kept alive, "jss_rule")`` of ``weights``: an
-        int32 tensor or array of shape (8,) -- one row for every env -- or (B, 8) -- env i uses row i --, on the host or on the
-        env's device; for ``kind="keys"`` the ``(JssKeys, array kept alive, "jss_key")`` of ``keys`` (``_keys_arg``).  The third
-        item is the prefix of the library's calls.  Anything else raises ValueError."""
-        if kind == "keys":
-            if weights is not None:
-                raise ValueError(f"{what}: weights= goes with kind='weighted'")
-            return self._keys_arg(keys, nope_key, what)
-        if keys is not None or nope_key is not None:
+    # -- the selector of a call: a stock rule, the caller's weighted rule or the caller's key tables ------------------------
+    def _selector(self, kind, what, weights=None, keys=None, nope_key=None):
+        """The ``_Selector`` of a policy / rollout / lookahead call.  ``kind="weighted"`` (include/jss_rules.h): ``weights`` is an
+        int32 tensor or array of shape (8,) -- one row for every env -- or (B, 8) -- env i uses row i; ``kind="keys"``
+        (include/jss_keys.h): ``keys`` is one of shape (jmax, mmax) -- one table for every env -- or (B, jmax, mmax) -- env i uses
+        table i --, ``nope_key`` NOPE's key (None = INT32_MIN: NOPE only when no job is legal); both on the host or on the env's
+        device.  Any other ``kind`` is a stock rule's name or code.  Anything else raises ValueError."""
+        if kind != "keys" and (keys is not None or nope_key is not None):
             raise ValueError(f"{what}: keys= and nope_key= go with kind='keys'")
-        if kind != "weighted":
-            if weights is not None:
-                raise ValueError(f"{what}: weights= goes with kind='weighted'")
-            return None
+        if kind != "weighted" and weights is not None:
+            raise ValueError(f"{what}: weights= goes with kind='weighted'")
+        if kind != "weighted" and kind != "keys":
+            sel = _STOCK.get(kind)
+            return sel if sel is not None else _STOCK.setdefault(kind, _Selector(_abi.policy_code(kind)))
+        weighted = kind == "weighted"
         if self._session is not None and not self._session.closed:
-            raise NotImplementedError(f"{what}: weighted rules do not run while a step session is open on the env")
-        be = self.backend
-        dt = getattr(weights, "dtype", None)
-        if dt is None or str(dt).split(".")[-1] != "int32":
-            raise ValueError(f"{what}: weights must be an int32 tensor or array of shape (8,) or ({self.batch}, 8) -- "
-                             "quantise float weights yourself (scale, round)")
-        shape = tuple(weights.shape)
-        if shape != (_abi.RW_N,) and shape != (self.batch, _abi.RW_N):
-            raise ValueError(f"{what}: weights must have shape (8,) or ({self.batch}, 8), got {shape}")
-        if not hasattr(be.lib, "jss_rule_policy"):
-            raise RuntimeError(f"{what}: the loaded library does not export the jss_rule_* calls of include/jss_rules.h")
-        if be.lib.jss_rule_policy.argtypes is None:                      # a library bound without include/jss_rules.h so far
-            _abi.bind_rules(be.lib)
-        w = be.as_device(weights, "int32")
-        if getattr(be, "torch", None) is None:
-            w = np.array(w, copy=True)                                   # (as_device keeps one array alive: this one is ours)
-        elif be.ptr(w) % 16:
-            w = w.clone()                                                # (a view at an odd offset: rows are read 16 bytes at a time)
-        return _abi.JssRule(be.ptr(w), _abi.RW_N if len(shape) == 2 else 0), w, "jss_rule"
-
-    # -- per-operation priority keys (include/jss_keys.h) ---------------------------------------------------------------
-    def _keys_arg(self, keys, nope_key, what):
-        """The ``(JssKeys, array kept alive, "jss_key")`` of ``keys``: an int32 tensor or array of shape (jmax, mmax) -- one
-        table for every env -- or (B, jmax, mmax) -- env i uses table i --, on the host or on the env's device; ``nope_key``:
-        NOPE's key, None = INT32_MIN, NOPE only when no job is legal."""
-        if self._session is not None and not self._session.closed:
-            raise NotImplementedError(f"{what}: key tables do not run while a step session is open on the env")
-        be = self.backend
-        J, M = self.jmax, self.mmax
-        dt = getattr(keys, "dtype", None)
-        if dt is None or str(dt).split(".")[-1] != "int32":
-            raise ValueError(f"{what}: keys must be an int32 tensor or array of shape ({J}, {M}) or ({self.batch}, {J}, {M}) -- "
-                             "dispatching.keys_from_floats maps float priorities")
-        shape = tuple(keys.shape)
-        if shape != (J, M) and shape != (self.batch, J, M):
-            raise ValueError(f"{what}: keys must have shape ({J}, {M}) or ({self.batch}, {J}, {M}), got {shape}")
+            raise NotImplementedError(f"{what}: {'weighted rules' if weighted else 'key tables'} do not run while a step session "
+                                      "is open on the env")
+        be, B, J, M = self.backend, self.batch, self.jmax, self.mmax
+        # per kind: the argument, its name, the shape of one row / table, how the messages word the two shapes, and a hint
+        if weighted:
+            x, name, one, forms, hint = weights, "weights", (_abi.RW_N,), "(8,) or ({B}, 8)", "quantise float weights yourself (scale, round)"
+        else:
+            x, name, one, forms, hint = keys, "keys", (J, M), "({J}, {M}) or ({B}, {J}, {M})", "dispatching.keys_from_floats maps float priorities"
+        dt = getattr(x, "dtype", None)
+        if dt is None or not (dt == np.int32 or str(dt).split(".")[-1] == "int32"):      # (NumPy's own: without the string)
+            raise ValueError(f"{what}: {name} must be an int32 tensor or array of shape {forms.format(B=B, J=J, M=M)} -- {hint}")
+        shape = tuple(x.shape)
+        if shape != one and shape != (B,) + one:
+            raise ValueError(f"{what}: {name} must have shape {forms.format(B=B, J=J, M=M)}, got {shape}")
         nope = _abi.KEY_NEVER_NOPE if nope_key is None else int(nope_key)
         if not -2**31 <= nope < 2**31:
             raise ValueError(f"{what}: nope_key must be in the int32 range")
-        if not hasattr(be.lib, "jss_key_policy"):
-            raise RuntimeError(f"{what}: the loaded library does not export the jss_key_* calls of include/jss_keys.h")
-        if be.lib.jss_key_policy.argtypes is None:                       # a library bound without include/jss_keys.h so far
-            _abi.bind_keys(be.lib)
-        k = be.as_device(keys, "int32")
+        family = "jss_rule" if weighted else "jss_key"
+        _abi.ensure_bound(be.lib, family, what)
+        a = be.as_device(x, "int32")
         if getattr(be, "torch", None) is None:
-            k = np.array(k, copy=True)                                   # (as_device keeps one array alive: this one is ours)
-        return _abi.JssKeys(be.ptr(k), J * M if len(shape) == 3 else 0, nope), k, "jss_key"
+            a = np.array(a, copy=True)                                   # (as_device keeps one array alive: this one is ours)
+        elif weighted and be.ptr(a) % 16:
+            a = a.clone()                                                # (a view at an odd offset: rows are read 16 bytes at a time)
+        stride = 0 if shape == one else _abi.RW_N if weighted else J * M
+        return _Selector(_abi.JssRule(be.ptr(a), stride) if weighted else _abi.JssKeys(be.ptr(a), stride, nope), a, family)
 
     # -- raw ABI handles (bench.py launches through these) -------------------------------
     @property
@@ -887,35 +898,24 @@ class BatchedJssEnv:
         if not self._is_reset:
             raise RuntimeError("call reset() before policy()")
         be = self.backend
-        rule = self._rule_arg(kind, weights, "policy", keys, nope_key)
-        if rule:
-            if cr_factor is not None:
-                raise ValueError("cr_factor is CriticalRatio's due-date factor: a positive float, with kind 'CR'")
-            d, s, _ = self._refs()
-            with be.on_device():
-                call = getattr(be.lib, rule[2] + "_policy")
-                _abi.check(be.lib, call(d, s, C.byref(rule[0]), self.seed if seed is None else int(seed),
-                                        int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()), rule[2] + "_policy")
-            return self._actions_out
-        k = _abi.policy_code(kind)
+        sel = self._selector(kind, "policy", weights, keys, nope_key)
         if cr_factor is not None:
-            if (k & 0xFF) != _abi.POLICY["CR"] or not 0.0 < float(cr_factor) < 1e300:
+            if not sel.stock or (sel.arg & 0xFF) != _abi.POLICY["CR"] or not 0.0 < float(cr_factor) < 1e300:
                 raise ValueError("cr_factor is CriticalRatio's due-date factor: a positive float, with kind 'CR'")
-            k = _abi.POLICY_CR_F64
+            sel = _Selector(_abi.POLICY_CR_F64)
             self._desc.cr_factor = float(cr_factor)
         d, s, _ = self._refs()
+        sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
         with be.on_device():
-            if self._classes is not None:
+            if sel.stock and self._classes is not None:
                 cs = self._classes["sets"]
                 for x in self._classes["keep"][0]:
                     x.cr_factor = self._desc.cr_factor
-                rc = be.lib.jss_multi_policy(self._classes["n"], cs[0], cs[1], k, self.seed if seed is None else int(seed),
-                                             int(round(explore * 65536)), self._class_ptrs(self._actions_out), be.stream())
+                rc = be.lib.jss_multi_policy(self._classes["n"], cs[0], cs[1], sel.arg, sd, q16,
+                                             self._class_ptrs(self._actions_out), be.stream())
                 _abi.check(be.lib, rc, "jss_multi_policy")
             else:
-                _abi.check(be.lib, be.lib.jss_policy(d, s, k, self.seed if seed is None else int(seed),
-                                                     int(round(explore * 65536)), be.ptr(self._actions_out), be.stream()),
-                           "jss_policy")
+                sel.call(be.lib, "policy", (d, s), sd, q16, be.ptr(self._actions_out), be.stream())
         return self._actions_out
 
     def _logits_arg(self, logits):
@@ -1018,34 +1018,27 @@ class BatchedJssEnv:
         if not self._is_reset:
             raise RuntimeError("call reset() before rollout()")
         be = self.backend
-        rule = self._rule_arg(kind, weights, "rollout", keys, nope_key)
-        if rule:
-            flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
-            d, s, o = self._refs()
-            if autoreset and self.fresh:
-                self._refuse_fresh(f"rollout(kind='{kind}', autoreset=True)")
-            with be.on_device():
-                rc = getattr(be.lib, rule[2] + "_rollout")(d, s, o, C.byref(rule[0]), self.seed if seed is None else int(seed),
-                                                           int(round(explore * 65536)), int(n_iter), flags, be.stream())
-                _abi.check(be.lib, rc, rule[2] + "_rollout")
-            return self._obs(), self.reward, self.done, False, {}
-        k = _abi.policy_code(kind)
-        flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
+        sel = self._selector(kind, "rollout", weights, keys, nope_key)
+        n_iter, flags = int(n_iter), _abi.ROLLOUT_AUTORESET if autoreset else 0
         d, s, o = self._refs()
         if autoreset and self.fresh:
-            if int(n_iter) > 1:
+            if not sel.stock:
+                self._refuse_fresh(f"rollout(kind='{kind}', autoreset=True)")
+            if n_iter > 1:
                 self._refuse_fresh("rollout(n_iter > 1, autoreset=True)")
             self.generate(self.done)      # one iteration: it restarts exactly the envs found done
-        with be.on_device():
-            if self._classes is not None and int(n_iter) == 1:
-                streams = (C.c_void_p * 1)(be.stream())
-                rc = be.lib.jss_multi_rollout(self._classes["n"], *self._classes["sets"], k, self.seed if seed is None else int(seed),
-                                              int(round(explore * 65536)), 1, flags, 1, streams)
-                _abi.check(be.lib, rc, "jss_multi_rollout")
-                return self._obs(), self.reward, self.done, False, {}
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
-        # (by shape class: one launch per range -- below 64 jobs / the rest -- with the kernel of its shape)
-        self._over_ranges(lambda dk, sk, ok, _a, stream: be.lib.jss_rollout(dk, sk, ok, k, sd, q16, int(n_iter), flags, stream), "jss_rollout")
+        if not sel.stock or self._classes is None:    # (the caller's selectors on a batch by shape class: the padded extents' kernel)
+            with be.on_device():
+                sel.call(be.lib, "rollout", (d, s, o), sd, q16, n_iter, flags, be.stream())
+        elif n_iter == 1:                             # by shape class: one grid over the classes
+            with be.on_device():
+                streams = (C.c_void_p * 1)(be.stream())
+                rc = be.lib.jss_multi_rollout(self._classes["n"], *self._classes["sets"], sel.arg, sd, q16, 1, flags, 1, streams)
+                _abi.check(be.lib, rc, "jss_multi_rollout")
+        else:                                         # ... one launch per range -- below 64 jobs / the rest -- with the kernel of its shape
+            self._over_ranges(lambda dk, sk, ok, _a, stream: be.lib.jss_rollout(dk, sk, ok, sel.arg, sd, q16, n_iter, flags, stream),
+                              "jss_rollout")
         return self._obs(), self.reward, self.done, False, {}
 
     def rollout_steps(self, kind: Union[str, int] = "random", steps: int = 1, n_sub: int = 2, seed: Optional[int] = None,
@@ -1061,7 +1054,7 @@ class BatchedJssEnv:
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
-        k = self._stock_code(kind, "rollout_steps")
+        k = stock_code(kind, "rollout_steps")
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         d, s, o = self._refs()
         sd = self.seed if seed is None else int(seed)
@@ -1095,7 +1088,7 @@ class BatchedJssEnv:
         if not 1 <= int(n_sub) <= _abi.MAX_SUB_BATCHES:
             raise ValueError(f"n_sub must be in [1, {_abi.MAX_SUB_BATCHES}]")
         be = self.backend
-        k = self._stock_code(kind, "policy_step_steps")
+        k = stock_code(kind, "policy_step_steps")
         flags = (_abi.ROLLOUT_AUTORESET if autoreset else 0)
         d, s, o = self._refs()
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
@@ -1125,7 +1118,7 @@ class BatchedJssEnv:
         be = self.backend
         if not hasattr(be, "stream_array"):
             return lambda: self.rollout_steps(kind, steps, n_sub, seed, autoreset, explore)
-        k = self._stock_code(kind, "bind_rollout_steps")
+        k = stock_code(kind, "bind_rollout_steps")
         flags = (_abi.ROLLOUT_AUTORESET if autoreset else 0) | (0 if caller_orders_streams else _abi.ROLLOUT_FORK_JOIN)
         d, s, o = self._refs()
         with be.on_device():
@@ -1178,7 +1171,7 @@ class BatchedJssEnv:
                 shape, dtype = shapes[name]
                 t = None if buffers is None else buffers.get(name)
                 out[name] = t if t is not None and tuple(t.shape) == shape else be.zeros(shape, dtype)
-        k = self._stock_code(kind, "trajectory")
+        k = stock_code(kind, "trajectory")
         flags = _abi.ROLLOUT_AUTORESET if autoreset else 0
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
         # (by shape class: one launch per range of the batch -- below 64 jobs / the rest -- each with the kernel of ITS shape,

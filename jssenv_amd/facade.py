@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _abi
-from .env import BatchedJssEnv
+from .env import BatchedJssEnv, play_to_end
 from .instances import resolve_instance
 
 
@@ -353,15 +353,12 @@ class JssEnv(gymnasium_base("Env")):
         b.reset()
         b.zero_counters()
         self._alloc_log, self._alloc_log_ok = [], False      # the device picks the actions: no per-call log (next_jobs)
-        chunk = self.jobs * self.machines + 16
-        for _ in range(64):
-            b.rollout(kind, n_iter=chunk, autoreset=False, explore=explore, weights=weights, keys=keys, nope_key=nope_key)
+
+        def done():                                          # (from the host snapshot that the results below are read from)
             self._cache = None
-            h = self._h()
-            if h["done"]:
-                break
-        else:
-            raise RuntimeError("episode did not finish")
+            return self._h()["done"]
+        play_to_end(b, kind, explore, done, "episode", weights=weights, keys=keys, nope_key=nope_key)
+        h = self._h()
         self._raise_for(h["err"])
         self.last_time_step = h["clock"]
         self.last_solution = self._solution()

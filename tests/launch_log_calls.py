@@ -188,10 +188,33 @@ def calls(lib, search):
             yield f"clone {layout} {n_dst} <- 333", lambda a=(byref(dd), byref(state()), byref(out()), byref(dst), byref(sd), byref(
                 state()), byref(out())): lib.jss_clone(*a, ptr(), STREAM)
 
+    # ---- the caller's selectors: weighted rules and key tables ---------------------------------------------------------
+    # (the four kernel shapes, the batch's instances in one shared table and in per-env tables, one weight row / key table for
+    #  every env and one per env; rollouts of one iteration and of several; lookahead with candidates and with none)
+    for shape in SHAPES:
+        J, M = SHAPES[shape]
+        for layout in ("shared-full", "own-full"):
+            for per_env in (False, True):
+                tag = f"{shape}/{layout}/b1000 {'per-env' if per_env else 'shared'}"
+                d, s, o = desc(1000, shape, layout), state(), out()
+                rule = _abi.JssRule(ptr(), _abi.RW_N if per_env else 0)
+                keys = _abi.JssKeys(ptr(), J * M if per_env else 0, _abi.KEY_NEVER_NOPE)
+                for family, sel in (("rule", rule), ("key", keys)):
+                    fn = lambda verb, family=family: getattr(lib, f"jss_{family}_{verb}")      # noqa: E731
+                    yield f"{family}_policy {tag}", lambda d=d, s=s, sel=sel, fn=fn: fn("policy")(
+                        byref(d), byref(s), byref(sel), 7, 0, ptr(), STREAM)
+                    for n_iter in (1, 5):
+                        yield f"{family}_rollout n_iter={n_iter} {tag}", lambda d=d, s=s, o=o, sel=sel, fn=fn, n=n_iter: fn("rollout")(
+                            byref(d), byref(s), byref(o), byref(sel), 7, 0, n, 0, STREAM)
+                    for n in (777, 0):
+                        la = _abi.JssLookahead(n=n, parent=ptr(), action=ptr(), id_base=0, makespan=ptr(), steps=ptr(), reward_num=ptr())
+                        yield f"{family}_lookahead n={n} {tag}", lambda d=d, s=s, la=la, sel=sel, fn=fn: fn("lookahead")(
+                            byref(d), byref(s), byref(la), byref(sel), 7, 0, 0, STREAM)
+
 
 def main(lib_path, log_path):
     lib = _abi.bind(C.CDLL(lib_path))
-    search = _abi.bind_search(lib)
+    search = _abi.bind_keys(_abi.bind_rules(_abi.bind_search(lib)))
     fd = os.open(log_path, os.O_WRONLY | os.O_APPEND | os.O_CREAT)
     for name, thunk in calls(lib, search):
         os.write(fd, f"# {name}\n".encode())

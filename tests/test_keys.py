@@ -55,7 +55,7 @@ def libs():
     out = {"twin": C.CDLL(build_cpu_twin()), "emu": C.CDLL(build_emu())}
     if not _has_gpu():              # no device: a row let through by mistake fails at its launch instead of reading host pointers
         out["hip"] = C.CDLL(build_extension())
-    return {k: _abi.bind_keys(_abi.bind_search(_abi.bind(v))) for k, v in out.items()}
+    return {k: _abi.ensure_bound(_abi.ensure_bound(_abi.bind(v), "jss"), "jss_key") for k, v in out.items()}
 
 
 # ---- 1. the boundary -----------------------------------------------------------------------------------------------------------------

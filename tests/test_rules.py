@@ -53,7 +53,7 @@ def libs():
     out = {"twin": C.CDLL(build_cpu_twin()), "emu": C.CDLL(build_emu())}
     if not _has_gpu():              # no device: a row let through by mistake fails at its launch instead of reading host pointers
         out["hip"] = C.CDLL(build_extension())
-    return {k: _abi.bind_rules(_abi.bind_search(_abi.bind(v))) for k, v in out.items()}
+    return {k: _abi.ensure_bound(_abi.ensure_bound(_abi.bind(v), "jss"), "jss_rule") for k, v in out.items()}
 
 
 # ---- 5. the boundary -----------------------------------------------------------------------------------------------------------------
