@@ -90,6 +90,12 @@ KEYS_VERSION = 1
 KEYS_SYMBOLS = ("jss_key_policy", "jss_key_rollout", "jss_key_lookahead")
 KEY_NEVER_NOPE = -2**31            # JssKeys.nope_key that exceeds no key: NOPE only when no job is legal
 
+# include/jss_beam.h: the companion header of beam search's candidate selection (its own version).  The HIP library exports it
+# from a library of its own, libjss_beam_hip.so; the twin from libjss_cpu.so.
+BEAM_VERSION = 1
+BEAM_SYMBOLS = ("jss_beam_select",)
+BEAM_DEDUPE = 1
+
 _p = C.c_void_p
 
 
@@ -145,6 +151,12 @@ class JssRule(C.Structure):          # include/jss_rules.h
 
 class JssKeys(C.Structure):          # include/jss_keys.h
     _fields_ = [("keys", _p), ("stride", C.c_int32), ("nope_key", C.c_int32)]
+
+
+class JssBeam(C.Structure):          # include/jss_beam.h
+    _fields_ = [("n_groups", C.c_int32), ("width", C.c_int32), ("n_actions", C.c_int32), ("flags", C.c_uint32),
+                ("cand_parent", _p), ("makespan", _p), ("steps", _p), ("reward_num", _p), ("done", _p), ("env_makespan", _p),
+                ("src", _p), ("action", _p), ("score", _p), ("next_parent", _p), ("counts", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -244,6 +256,15 @@ def bind_keys(lib):
     lib.jss_key_rollout.argtypes = [D, S, O, K, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _p]
     lib.jss_key_lookahead.restype = C.c_int
     lib.jss_key_lookahead.argtypes = [D, S, C.POINTER(JssLookahead), K, C.c_uint64, C.c_uint32, C.c_int32, _p]
+    return lib
+
+
+def bind_beam(lib):
+    """Attach the prototype of include/jss_beam.h; raises AttributeError naming the first missing symbol."""
+    for name in BEAM_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_beam_select.restype, lib.jss_beam_select.argtypes = C.c_int, [C.POINTER(JssBeam), _p]
     return lib
 
 

@@ -45,6 +45,17 @@ class HipBackend:
         self._scalars = {}
         self._stream_arrays = {}
         self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+        self._beam_lib = None
+
+    @property
+    def beam_lib(self):
+        """libjss_beam_hip.so (include/jss_beam.h), loaded on first use; a missing library is an error."""
+        if self._beam_lib is None:
+            path = _abi.library_path("libjss_beam_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            self._beam_lib = _abi.bind_beam(C.CDLL(path))
+        return self._beam_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -233,6 +244,11 @@ class CpuBackend:
             raise RuntimeError(f"{path} is not the CPU twin ({self.lib.jss_backend()!r})")
         self.threads = int(threads)
         self._keep = None
+
+    @property
+    def beam_lib(self):
+        """the library that exports include/jss_beam.h: the twin itself"""
+        return _abi.bind_beam(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -1,6 +1,7 @@
-"""Builds the two native libraries of the package, in-tree:
+"""Builds the native libraries of the package, in-tree:
 
 * ``libjss_hip.so``  -- the MI355X kernels + C ABI (hipcc, gfx950 only);
+* ``libjss_beam_hip.so`` -- beam search's selection kernel (include/jss_beam.h), a library of its own with the same flags;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -22,6 +23,9 @@ _HEADER = os.path.join(_ROOT, "include", "jss_hip.h")
 _SEARCH = os.path.join(_ROOT, "include", "jss_search.h")     # its companion: the search calls (jss_lookahead)
 _RULES = os.path.join(_ROOT, "include", "jss_rules.h")       # ... and the caller-weighted rules (jss_rule_*)
 _KEYS = os.path.join(_ROOT, "include", "jss_keys.h")         # ... and the per-operation priority keys (jss_key_*)
+_BEAM = os.path.join(_ROOT, "include", "jss_beam.h")         # ... and beam search's selection (jss_beam_select)
+BEAM_SRC = os.path.join(_HERE, "csrc", "jss_beam.hip")       # (libjss_beam_hip.so: its kernel stays out of libjss_hip.so)
+BEAM_OUT = os.path.join(_HERE, "libjss_beam_hip.so")
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -39,15 +43,26 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))] + [_HEADER, _SEARCH, _RULES, _KEYS]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f != os.path.basename(BEAM_SRC)] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM]
+    if out == OUT:                     # the default output: the package's second HIP library goes with it
+        build_beam_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
     return out
 
 
+def build_beam_extension(force: bool = False) -> str:
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM]):
+        return BEAM_OUT
+    tmp = BEAM_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
+    os.replace(tmp, BEAM_OUT)
+    return BEAM_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

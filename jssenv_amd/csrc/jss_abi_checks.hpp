@@ -13,6 +13,7 @@
 #include "jss_search.h"
 #include "jss_rules.h"
 #include "jss_keys.h"
+#include "jss_beam.h"
 
 namespace jss_abi {
 
@@ -325,6 +326,18 @@ inline int check_lookahead(const JssDesc *d, const JssState *s, const JssLookahe
     if (!la->parent || !la->action || !la->makespan) return JSS_E_NULL;
     if (la->n < 0 || n_iter < 0) return JSS_E_SHAPE;
     return check_selector(d, sel);
+}
+
+// ---- beam search (include/jss_beam.h) ------------------------------------------------------------------------------
+// jss_beam_select (libjss_beam_hip.so and the twin): width * n_actions <= 65536 -- a candidate's index within its group is half
+// of a 64-bit sort key, and one workgroup serves a group
+inline int check_beam_select(const JssBeam *b) {
+    if (!b) return JSS_E_NULL;
+    if (!b->cand_parent || !b->makespan || !b->steps || !b->reward_num || !b->done || !b->env_makespan || !b->src ||
+        !b->action || !b->score || !b->next_parent || !b->counts)
+        return JSS_E_NULL;
+    if (b->n_groups < 0 || b->width < 1 || b->n_actions < 2 || (int64_t)b->width * b->n_actions > 65536) return JSS_E_SHAPE;
+    return b->next_parent == b->cand_parent ? JSS_E_SHAPE : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

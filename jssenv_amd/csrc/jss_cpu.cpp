@@ -12,12 +12,16 @@
 // Reference semantics (JSSEnv/envs/jss_env.py, cited per function) in the queue-free form: the reference's
 // sorted event list is {t + tm[m] : tm[m] > 0}, its M x J illegal_actions matrix is blocked[j] && need[j] == m,
 // and nb_legal_actions / machine_legal / nb_machine_legal are functions of the legal flags.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <mutex>
+#include <set>
+#include <tuple>
 #include <unordered_map>
+#include <vector>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
@@ -1287,6 +1291,64 @@ int jss_clone(const JssDesc *dst_desc, const JssState *dst, const JssOut *dst_ou
         }
     };
     parallel_for(dd.batch, dd.threads, one);
+    return 0;
+}
+
+// include/jss_beam.h: a plain sort per group.  Walking the group's valid candidates in (makespan, c) order, the first one seen
+// of a triple is the one with the lowest c: a set of the triples seen is the header's dedupe rule.
+int jss_beam_select(const JssBeam *beam, void *) {
+    if (const int rc = check_beam_select(beam)) return rc;
+    const JssBeam b = *beam;
+    const int W = b.width, A = b.n_actions;
+    struct Cand {
+        int32_t makespan, c, steps, slot, action;
+        int64_t rnum;
+    };
+    auto group = [&](int g) {
+        const int s0 = g * W;
+        const size_t c0 = (size_t)s0 * A;
+        std::vector<Cand> cands;
+        int running = 0;
+        for (int w = 0; w < W; ++w) {
+            const int s = s0 + w;
+            const size_t row = c0 + (size_t)w * A;
+            if (b.cand_parent[row] != s) continue;
+            if (b.done[s]) {
+                cands.push_back({b.env_makespan[s], w * A, 0, s, JSS_ACTION_SKIP, 0});
+                continue;
+            }
+            ++running;
+            for (int a = 0; a < A; ++a)
+                if (b.makespan[row + a] >= 0) cands.push_back({b.makespan[row + a], w * A + a, b.steps[row + a], s, a, b.reward_num[row + a]});
+        }
+        int32_t *cnt = b.counts + (size_t)g * 4;
+        if (!running) {
+            std::copy(b.cand_parent + c0, b.cand_parent + c0 + (size_t)W * A, b.next_parent + c0);
+            for (int w = 0; w < W; ++w) b.src[s0 + w] = -1, b.action[s0 + w] = JSS_ACTION_SKIP, b.score[s0 + w] = -1;
+            cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+            return;
+        }
+        std::sort(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) {
+            return x.makespan != y.makespan ? x.makespan < y.makespan : x.c < y.c;
+        });
+        std::set<std::tuple<int32_t, int32_t, int64_t>> seen;
+        int filled = 0, dropped = 0;
+        for (const Cand &k : cands) {
+            if (filled == W) break;
+            if ((b.flags & JSS_BEAM_DEDUPE) && !seen.insert({k.makespan, k.steps, k.rnum}).second) {
+                ++dropped;
+                continue;
+            }
+            b.src[s0 + filled] = k.slot, b.action[s0 + filled] = k.action, b.score[s0 + filled] = k.makespan;
+            ++filled;
+        }
+        for (int w = 0; w < W; ++w) {
+            if (w >= filled) b.src[s0 + w] = -1, b.action[s0 + w] = JSS_ACTION_SKIP, b.score[s0 + w] = -1;
+            std::fill_n(b.next_parent + c0 + (size_t)w * A, A, w < filled ? s0 + w : -1);
+        }
+        cnt[0] = filled, cnt[1] = running, cnt[2] = dropped, cnt[3] = (int32_t)cands.size();
+    };
+    parallel_for(b.n_groups, 0, group);
     return 0;
 }
 
