@@ -96,6 +96,11 @@ BEAM_VERSION = 1
 BEAM_SYMBOLS = ("jss_beam_select",)
 BEAM_DEDUPE = 1
 
+# include/jss_bound.h: the companion header of the makespan lower bounds (its own version).  The HIP library exports it from a
+# third library, libjss_bound_hip.so; the twin from libjss_cpu.so.
+BOUND_VERSION = 1
+BOUND_SYMBOLS = ("jss_bound",)
+
 _p = C.c_void_p
 
 
@@ -157,6 +162,11 @@ class JssBeam(C.Structure):          # include/jss_beam.h
     _fields_ = [("n_groups", C.c_int32), ("width", C.c_int32), ("n_actions", C.c_int32), ("flags", C.c_uint32),
                 ("cand_parent", _p), ("makespan", _p), ("steps", _p), ("reward_num", _p), ("done", _p), ("env_makespan", _p),
                 ("src", _p), ("action", _p), ("score", _p), ("next_parent", _p), ("counts", _p)]
+
+
+class JssBound(C.Structure):         # include/jss_bound.h
+    _fields_ = [("n", C.c_int32), ("parent", _p), ("action", _p), ("mask", _p), ("lower_bound", _p), ("job_bound", _p),
+                ("est_start", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -265,6 +275,16 @@ def bind_beam(lib):
         if not hasattr(lib, name):
             raise AttributeError(f"library does not export {name}")
     lib.jss_beam_select.restype, lib.jss_beam_select.argtypes = C.c_int, [C.POINTER(JssBeam), _p]
+    return lib
+
+
+def bind_bound(lib):
+    """Attach the prototype of include/jss_bound.h; raises AttributeError naming the first missing symbol."""
+    for name in BOUND_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_bound.restype = C.c_int
+    lib.jss_bound.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBound), _p]
     return lib
 
 

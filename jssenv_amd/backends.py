@@ -46,6 +46,7 @@ class HipBackend:
         self._stream_arrays = {}
         self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._beam_lib = None
+        self._bound_lib = None
 
     @property
     def beam_lib(self):
@@ -56,6 +57,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
             self._beam_lib = _abi.bind_beam(C.CDLL(path))
         return self._beam_lib
+
+    @property
+    def bound_lib(self):
+        """libjss_bound_hip.so (include/jss_bound.h), loaded on first use; a missing library is an error."""
+        if self._bound_lib is None:
+            path = _abi.library_path("libjss_bound_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            self._bound_lib = _abi.bind_bound(C.CDLL(path))
+        return self._bound_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -249,6 +260,11 @@ class CpuBackend:
     def beam_lib(self):
         """the library that exports include/jss_beam.h: the twin itself"""
         return _abi.bind_beam(self.lib)
+
+    @property
+    def bound_lib(self):
+        """the library that exports include/jss_bound.h: the twin itself"""
+        return _abi.bind_bound(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

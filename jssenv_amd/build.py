@@ -2,6 +2,7 @@
 
 * ``libjss_hip.so``  -- the MI355X kernels + C ABI (hipcc, gfx950 only);
 * ``libjss_beam_hip.so`` -- beam search's selection kernel (include/jss_beam.h), a library of its own with the same flags;
+* ``libjss_bound_hip.so`` -- the lower-bound kernel (include/jss_bound.h), a third HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -26,6 +27,10 @@ _KEYS = os.path.join(_ROOT, "include", "jss_keys.h")         # ... and the per-o
 _BEAM = os.path.join(_ROOT, "include", "jss_beam.h")         # ... and beam search's selection (jss_beam_select)
 BEAM_SRC = os.path.join(_HERE, "csrc", "jss_beam.hip")       # (libjss_beam_hip.so: its kernel stays out of libjss_hip.so)
 BEAM_OUT = os.path.join(_HERE, "libjss_beam_hip.so")
+_BOUND = os.path.join(_ROOT, "include", "jss_bound.h")       # ... and the makespan lower bounds (jss_bound)
+BOUND_SRC = os.path.join(_HERE, "csrc", "jss_bound.hip")     # (libjss_bound_hip.so: a library of its own as well)
+BOUND_OUT = os.path.join(_HERE, "libjss_bound_hip.so")
+_OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -43,9 +48,10 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f != os.path.basename(BEAM_SRC)] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM]
-    if out == OUT:                     # the default output: the package's second HIP library goes with it
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]
+    if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
+        build_bound_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -53,7 +59,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -61,8 +67,17 @@ def build_beam_extension(force: bool = False) -> str:
     return BEAM_OUT
 
 
+def build_bound_extension(force: bool = False) -> str:
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
+        return BOUND_OUT
+    tmp = BOUND_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
+    os.replace(tmp, BOUND_OUT)
+    return BOUND_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -14,6 +14,7 @@
 #include "jss_rules.h"
 #include "jss_keys.h"
 #include "jss_beam.h"
+#include "jss_bound.h"
 
 namespace jss_abi {
 
@@ -338,6 +339,17 @@ inline int check_beam_select(const JssBeam *b) {
         return JSS_E_NULL;
     if (b->n_groups < 0 || b->width < 1 || b->n_actions < 2 || (int64_t)b->width * b->n_actions > 65536) return JSS_E_SHAPE;
     return b->next_parent == b->cand_parent ? JSS_E_SHAPE : 0;
+}
+
+// ---- lower bounds (include/jss_bound.h) ----------------------------------------------------------------------------
+// jss_bound (libjss_bound_hip.so and the twin): the batch as jss_lookahead checks it, and the work table, which the bound reads
+inline int check_bound(const JssDesc *d, const JssState *s, const JssBound *b) {
+    if (!d || !s || !b) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!d->rem || !b->lower_bound) return JSS_E_NULL;
+    if (b->n < 0 || (!b->parent && b->n != d->batch)) return JSS_E_SHAPE;
+    return 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

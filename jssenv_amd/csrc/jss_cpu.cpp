@@ -1352,4 +1352,82 @@ int jss_beam_select(const JssBeam *beam, void *) {
     return 0;
 }
 
+// include/jss_bound.h: the definition, candidate by candidate.  The candidate's move is applied to a private copy of the job's
+// scheduled prefix (its length and its end) and of the machines' release times; the solution itself is only read.
+int jss_bound(const JssDesc *desc, const JssState *state, const JssBound *bound, void *) {
+    if (const int rc = check_bound(desc, state, bound)) return rc;
+    const JssDesc d = *desc;
+    const JssBound b = *bound;
+    const size_t region = (size_t)d.jmax * d.mmax;
+    constexpr int kNone = std::numeric_limits<int32_t>::max();
+    auto one = [&](int c) {
+        const int parent = b.parent ? b.parent[c] : c, action = b.action ? b.action[c] : JSS_ACTION_SKIP;
+        auto none = [&] {
+            b.lower_bound[c] = -1;
+            if (b.job_bound) b.job_bound[c] = -1;
+        };
+        if (parent < 0 || parent >= d.batch) return none();
+        const int32_t *ec = state->env_const + (size_t)parent * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return none();
+        if (action < JSS_ACTION_SKIP || action > J) return none();
+        if (b.mask && action >= 0 && !b.mask[(size_t)parent * (d.jmax + 1) + action]) return none();
+        const int now = state->env[(size_t)parent * JSS_NH + JSS_H_CLOCK];
+        const int32_t *sol = state->solution + (size_t)parent * region;
+        const int32_t *ops = d.ops + (size_t)tab * region, *rem = d.rem + (size_t)tab * region;
+        int32_t n_sched[JSS_MAX_JOBS], job_end[JSS_MAX_JOBS], release[JSS_MAX_MACHINES] = {};
+        for (int j = 0; j < J; ++j) {
+            int s = 0, end = 0;
+            for (int k = 0; k < M && sol[j * d.mmax + k] >= 0; ++k) {
+                const int op = ops[j * d.mmax + k];
+                end = sol[j * d.mmax + k] + (op & 0xFFFF);
+                release[(op >> 16) & 63] = std::max(release[(op >> 16) & 63], end);
+                s = k + 1;
+            }
+            n_sched[j] = s, job_end[j] = end;
+        }
+        int moved_head = 0;
+        if (action >= 0 && action < J) {
+            const int s = n_sched[action];
+            if (s >= M) return none();
+            const int op = ops[action * d.mmax + s], m = (op >> 16) & 63;
+            moved_head = std::max(std::max(now, job_end[action]), release[m]);
+            job_end[action] = moved_head + (op & 0xFFFF);
+            release[m] = std::max(release[m], job_end[action]);
+            n_sched[action] = s + 1;
+        }
+        int32_t *est = b.est_start ? b.est_start + (size_t)c * region : nullptr;
+        if (est) {
+            std::fill_n(est, region, -1);
+            for (int j = 0; j < J; ++j)
+                for (int k = 0; k < n_sched[j]; ++k) est[j * d.mmax + k] = sol[j * d.mmax + k];
+            if (action >= 0 && action < J) est[action * d.mmax + n_sched[action] - 1] = moved_head;
+        }
+        int32_t min_head[JSS_MAX_MACHINES], sum_dur[JSS_MAX_MACHINES] = {}, min_tail[JSS_MAX_MACHINES];
+        std::fill_n(min_head, JSS_MAX_MACHINES, kNone);
+        std::fill_n(min_tail, JSS_MAX_MACHINES, kNone);
+        int job_bound = 0;
+        for (int j = 0; j < J; ++j) {
+            int ready = std::max(now, job_end[j]);
+            for (int k = n_sched[j]; k < M; ++k) {
+                const int op = ops[j * d.mmax + k], m = (op >> 16) & 63, dur = op & 0xFFFF;
+                const int head = std::max(ready, release[m]);
+                ready = head + dur;
+                if (est) est[j * d.mmax + k] = head;
+                min_head[m] = std::min(min_head[m], head);
+                sum_dur[m] += dur;
+                min_tail[m] = std::min(min_tail[m], rem[j * d.mmax + k] - dur);
+            }
+            job_bound = std::max(job_bound, n_sched[j] >= M ? job_end[j] : ready);
+        }
+        int lower = job_bound;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            if (min_head[m] != kNone) lower = std::max(lower, min_head[m] + sum_dur[m] + min_tail[m]);
+        b.lower_bound[c] = lower;
+        if (b.job_bound) b.job_bound[c] = job_bound;
+    };
+    parallel_for(b.n, d.threads, one);
+    return 0;
+}
+
 }  // extern "C"

@@ -719,6 +719,76 @@ class BatchedJssEnv:
                 ret = np.where(mto > 0, rnum / np.maximum(mto, 1), 0.0).astype(np.float32)
         return makespan.reshape(shape), steps.reshape(shape), ret.reshape(shape)
 
+    # -- makespan lower bounds of states and of candidate moves (jss_bound, include/jss_bound.h) ----------------------------
+    def lower_bound(self, actions=None, parents=None, legal_only: bool = True, job_bound: bool = False, est_start: bool = False):
+        """A lower bound of the makespan of EVERY completion of a state, or of a state after one more move: the larger of the
+        longest job's earliest end and, per machine, earliest head + remaining work on it + shortest tail (include/jss_bound.h
+        defines it; integers, the same bits on every backend).  Where ``lookahead`` pays for a rollout and returns an upper
+        bound, this reads the clock, the solution and the instance tables once; the batch is not touched.
+
+        No arguments: the states' own bounds, int32 ``(B,)``.  ``actions="all"``: every column of every env in ``lookahead``'s
+        parent-major order, ``(B, jmax + 1)`` -- job a takes its next operation at its earliest start, column J (NOPE) is the
+        state's own bound, columns behind J are -1.  ``parents`` / ``actions`` (host or device int sequences of equal length, -1
+        = no move): ``(n,)``.  -1 marks what cannot be evaluated: a parent out of range or never reset, an action outside
+        [-1, J], a job with no operation left, and -- with ``legal_only`` -- an action that ``action_mask`` does not allow.
+        A done env's bound is its makespan.
+        ``job_bound=True`` adds the job term alone, ``est_start=True`` the per-operation earliest starts ``(..., jmax, mmax)``
+        (a scheduled operation's start, -1 in the padding; rows of refused candidates are -1 throughout): the result is then
+        the tuple ``(lower_bound[, job_bound][, est_start])``.  Arrays of the env's backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before lower_bound()")
+        self._no_open_session("lower_bound")
+        from .search import bound_library
+        be = self.backend
+        lib = bound_library(be)
+        B, A = self.batch, self.jmax + 1
+        every = isinstance(actions, str)
+        if every and (actions != "all" or parents is not None):
+            raise ValueError("lower_bound: actions is 'all' (without parents), an array given with parents, or None")
+        if not every and (actions is None) != (parents is None):
+            raise ValueError("lower_bound: give both parents and actions, actions='all', or neither (the states' own bounds)")
+        t = getattr(be, "torch", None)
+        with be.on_device():
+            par = act = None
+            if every:
+                shape = (B, A)
+                if t is not None:
+                    par = t.arange(B, dtype=t.int32, device=be.device).repeat_interleave(A)
+                    act = t.arange(A, dtype=t.int32, device=be.device).repeat(B)
+                else:
+                    par = np.repeat(np.arange(B, dtype=np.int32), A)
+                    act = np.tile(np.arange(A, dtype=np.int32), B)
+            elif parents is not None:
+                par, act = be.as_device(parents, "int32"), be.as_device(actions, "int32")
+                if t is None:
+                    par, act = par.copy(), act.copy()          # (as_device keeps one array alive: the second would drop the first)
+                if par.ndim != 1 or tuple(par.shape) != tuple(act.shape):
+                    raise ValueError("lower_bound: parents and actions must be 1-d and of equal length")
+                shape = (int(par.shape[0]),)
+            else:
+                shape = (B,)
+            n = int(np.prod(shape))
+            lower = be.zeros((n,), "int32")
+            jb = be.zeros((n,), "int32") if job_bound else None
+            est = None
+            if est_start:
+                est = be.zeros((n, self.jmax, self.mmax), "int32")
+                est -= 1
+            if n:
+                p = be.ptr
+                arg = _abi.JssBound(n, p(par), p(act), p(self.action_mask) if (legal_only and act is not None) else None, p(lower),
+                                    p(jb), p(est))
+                rc = lib.jss_bound(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_bound")
+            self._bound_keep = (par, act)                      # alive until the launch has read them
+        out = (lower.reshape(shape),)
+        if job_bound:
+            out += (jb.reshape(shape),)
+        if est_start:
+            out += (est.reshape(shape + (self.jmax, self.mmax)),)
+        return out[0] if len(out) == 1 else out
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

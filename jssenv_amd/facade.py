@@ -314,6 +314,12 @@ class JssEnv(gymnasium_base("Env")):
         self._raise_for(self._h()["err"])
         return hole
 
+    def lower_bound(self) -> int:
+        """A lower bound of the makespan of every completion of the current state (``BatchedJssEnv.lower_bound``,
+        include/jss_bound.h): the makespan itself once the episode is done."""
+        b = self._b
+        return int(b.backend.numpy(b.lower_bound())[0])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

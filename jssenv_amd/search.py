@@ -5,6 +5,9 @@ rollout (``jss_lookahead``), keeps the W best candidates of every problem -- dup
 the chosen envs into the slots (``jss_clone``) and steps them by the chosen actions (``jss_step``).  The results are defined by
 those calls alone: ``beam_select_reference`` is the selection written in NumPy, and the loop of ``beam_search`` written with
 ``lookahead``, ``beam_select_reference``, ``copy_from`` and ``step`` gives the same bytes (tests/beam_cases.py does that).
+
+Also here: ``lower_bound_reference``, the NumPy mirror of ``jss_bound`` (include/jss_bound.h: makespan lower bounds of states and
+of candidate moves, per-operation earliest starts), and ``bound_library``; ``BatchedJssEnv.lower_bound`` is the call.
 """
 from __future__ import annotations
 
@@ -132,6 +135,112 @@ def lookahead_into(env, sel, cand_parent, actions, makespan, steps, reward_num, 
     p = be.ptr
     la = _abi.JssLookahead(int(np.prod(tuple(makespan.shape))), p(cand_parent), p(actions), 0, p(makespan), p(steps), p(reward_num))
     sel.call(be.lib, "lookahead", (C.byref(env._desc), C.byref(env._state), C.byref(la)), seed, explore_q16, n_iter, be.stream())
+
+
+# ---- makespan lower bounds (include/jss_bound.h), in NumPy ----------------------------------------------------------------
+def bound_library(backend):
+    """The library of ``backend`` that exports include/jss_bound.h: ``backend.bound_lib`` (HipBackend: libjss_bound_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
+    lib = getattr(backend, "bound_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not hasattr(lib, "jss_bound"):
+            raise RuntimeError("lower_bound: the backend's library does not export jss_bound (include/jss_bound.h)")
+        _abi.bind_bound(lib)
+    return lib
+
+
+def lower_bound_reference(env_header, env_const, solution, ops, rem, parents=None, actions=None, mask=None, est_fill=None,
+                          block=256):
+    """include/jss_bound.h's semantics on host arrays, written from the header's definition (all candidates of a block at once,
+    one pass per operation index; the per-machine terms by ``ufunc.at``).  ``env_header`` (B, 4), ``env_const`` (B, 12),
+    ``solution`` (B, jmax, mmax), ``ops`` / ``rem`` (n_tables, jmax, mmax); ``parents`` / ``actions`` (n,) or None (every env;
+    no move); ``mask`` (B, jmax + 1) or None.  Returns ``(lower_bound, job_bound, est_start)``: int32 (n,), (n,) and
+    (n, jmax, mmax) -- the last one None unless ``est_fill`` is given, the value rows of refused candidates keep."""
+    hdr = np.asarray(env_header, dtype=np.int64).reshape(-1, _abi.NH)
+    B = hdr.shape[0]
+    const = np.asarray(env_const, dtype=np.int64).reshape(B, _abi.NC)
+    sol_all = np.asarray(solution, dtype=np.int64)
+    jmax, mmax = sol_all.shape[-2:]
+    sol_all = sol_all.reshape(B, jmax, mmax)
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    rem = np.asarray(rem, dtype=np.int64).reshape(-1, jmax, mmax)
+    parents = np.arange(B, dtype=np.int64) if parents is None else np.asarray(parents, dtype=np.int64).reshape(-1)
+    n = parents.size
+    actions = np.full(n, SKIP, np.int64) if actions is None else np.asarray(actions, dtype=np.int64).reshape(-1)
+    lower, jobb = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    est = None if est_fill is None else np.full((n, jmax, mmax), est_fill, np.int32)
+    ok = (parents >= 0) & (parents < B)
+    par = np.where(ok, parents, 0)
+    ok &= const[par, _abi.C_JOBS] > 0
+    ok &= (actions >= SKIP) & (actions <= const[par, _abi.C_JOBS])
+    if mask is not None:
+        mask = np.asarray(mask).reshape(B, jmax + 1)
+        ok &= (actions < 0) | (mask[par, np.clip(actions, 0, jmax)] != 0)
+    BIG = np.int64(2) ** 40
+    kk = np.arange(mmax)
+
+    def prefix(S, D, real):
+        """scheduled flags, s_j and jobend_j of solutions S (v, jmax, mmax)"""
+        sched = real & (S >= 0)
+        s = sched.sum(axis=2)
+        last = np.take_along_axis(S + D, np.maximum(s - 1, 0)[:, :, None], axis=2)[:, :, 0]
+        return sched, s, np.where(s > 0, last, 0)
+
+    def releases(S, D, mach, sched):
+        r = np.zeros((S.shape[0], _abi.MAX_MACHINES), np.int64)
+        v = np.nonzero(sched)
+        np.maximum.at(r, (v[0], mach[v]), (S + D)[v])
+        return r
+
+    for lo in range(0, n, block):
+        idx = lo + np.flatnonzero(ok[lo:lo + block])
+        if idx.size == 0:
+            continue
+        p, a = par[idx], actions[idx]
+        J, M, tab, t = const[p, _abi.C_JOBS], const[p, _abi.C_MACHINES], const[p, _abi.C_TABLE], hdr[p, _abi.H_CLOCK]
+        S = sol_all[p].copy()
+        D, mach, R = ops[tab] & 0xFFFF, ops[tab] >> 16, rem[tab]
+        real = (np.arange(jmax)[None, :, None] < J[:, None, None]) & (kk[None, None, :] < M[:, None, None])
+        rows = np.arange(idx.size)
+        sched, s, jobend = prefix(S, D, real)
+        # the candidate's move: sol[a][s_a] = h(a, s_a), with the parent's clock
+        job = (a >= 0) & (a < J)
+        aj = np.where(job, a, 0)
+        s_a = s[rows, aj]
+        good = ~(job & (s_a >= M))                                    # a job with no operation left: refused
+        mv = np.flatnonzero(job & good)
+        if mv.size:
+            r = releases(S, D, mach, sched)
+            m_a = mach[mv, aj[mv], s_a[mv]]
+            S[mv, aj[mv], s_a[mv]] = np.maximum(np.maximum(t[mv], jobend[mv, aj[mv]]), r[mv, m_a])
+            sched, s, jobend = prefix(S, D, real)
+        r = releases(S, D, mach, sched)
+        # heads, operation index by operation index
+        H = np.zeros_like(S)
+        for k in range(mmax):
+            rk = np.take_along_axis(r, mach[:, :, k], axis=1)
+            first = np.maximum(np.maximum(t[:, None], jobend), rk)
+            chain = np.maximum(H[:, :, k - 1] + D[:, :, k - 1], rk) if k else first
+            H[:, :, k] = np.where(sched[:, :, k], S[:, :, k], np.where(s == k, first, chain))
+        last = (M - 1)[:, None, None]
+        ends = (np.take_along_axis(H, last, axis=2) + np.take_along_axis(D, last, axis=2))[:, :, 0]
+        jb = np.where(np.arange(jmax)[None, :] < J[:, None], ends, 0).max(axis=1)
+        # per machine: min h + sum d + min tail over the unscheduled ops
+        minh = np.full((idx.size, _abi.MAX_MACHINES), BIG)
+        sumd = np.zeros_like(minh)
+        mint = np.full_like(minh, BIG)
+        u = np.nonzero(real & ~sched)
+        np.minimum.at(minh, (u[0], mach[u]), H[u])
+        np.add.at(sumd, (u[0], mach[u]), D[u])
+        np.minimum.at(mint, (u[0], mach[u]), (R - D)[u])
+        lbm = np.where(minh < BIG, minh + sumd + mint, -1).max(axis=1)
+        g = np.flatnonzero(good)
+        lower[idx[g]] = np.maximum(jb, lbm)[g]
+        jobb[idx[g]] = jb[g]
+        if est is not None:
+            est[idx[g]] = np.where(real, H, -1)[g]
+    return lower, jobb, est
 
 
 # ---- the driver ------------------------------------------------------------------------------------------------------------
