@@ -101,6 +101,11 @@ BEAM_DEDUPE = 1
 BOUND_VERSION = 1
 BOUND_SYMBOLS = ("jss_bound",)
 
+# include/jss_order.h: the companion header of the evaluation of machine orders (its own version).  The HIP library exports it
+# from a fourth library, libjss_order_hip.so; the twin from libjss_cpu.so.
+ORDER_VERSION = 1
+ORDER_SYMBOLS = ("jss_order_eval", "jss_order_apply")
+
 _p = C.c_void_p
 
 
@@ -167,6 +172,16 @@ class JssBeam(C.Structure):          # include/jss_beam.h
 class JssBound(C.Structure):         # include/jss_bound.h
     _fields_ = [("n", C.c_int32), ("parent", _p), ("action", _p), ("mask", _p), ("lower_bound", _p), ("job_bound", _p),
                 ("est_start", _p)]
+
+
+class JssOrder(C.Structure):         # include/jss_order.h
+    _fields_ = [("n", C.c_int32), ("pair_cap", C.c_int32), ("rank", _p), ("parent", _p), ("swap_a", _p), ("swap_b", _p),
+                ("makespan", _p), ("start", _p), ("tail", _p), ("pair_a", _p), ("pair_b", _p), ("n_pairs", _p)]
+
+
+class JssOrderApply(C.Structure):    # include/jss_order.h
+    _fields_ = [("batch", C.c_int32), ("jmax", C.c_int32), ("mmax", C.c_int32), ("pair_cap", C.c_int32), ("rank", _p), ("cur", _p),
+                ("makespan", _p), ("pair_a", _p), ("pair_b", _p), ("improved", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -285,6 +300,18 @@ def bind_bound(lib):
             raise AttributeError(f"library does not export {name}")
     lib.jss_bound.restype = C.c_int
     lib.jss_bound.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBound), _p]
+    return lib
+
+
+def bind_order(lib):
+    """Attach the prototypes of include/jss_order.h; raises AttributeError naming the first missing symbol."""
+    for name in ORDER_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_order_eval.restype = C.c_int
+    lib.jss_order_eval.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssOrder), _p]
+    lib.jss_order_apply.restype = C.c_int
+    lib.jss_order_apply.argtypes = [C.POINTER(JssOrderApply), _p]
     return lib
 
 

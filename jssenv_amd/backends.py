@@ -47,6 +47,7 @@ class HipBackend:
         self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._beam_lib = None
         self._bound_lib = None
+        self._order_lib = None
 
     @property
     def beam_lib(self):
@@ -67,6 +68,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
             self._bound_lib = _abi.bind_bound(C.CDLL(path))
         return self._bound_lib
+
+    @property
+    def order_lib(self):
+        """libjss_order_hip.so (include/jss_order.h), loaded on first use; a missing library is an error."""
+        if self._order_lib is None:
+            path = _abi.library_path("libjss_order_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            self._order_lib = _abi.bind_order(C.CDLL(path))
+        return self._order_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -265,6 +276,11 @@ class CpuBackend:
     def bound_lib(self):
         """the library that exports include/jss_bound.h: the twin itself"""
         return _abi.bind_bound(self.lib)
+
+    @property
+    def order_lib(self):
+        """the library that exports include/jss_order.h: the twin itself"""
+        return _abi.bind_order(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -210,6 +210,10 @@ class BucketedJssEnv:
             b._logits_keep = a[3]                    # alive until the launch has read it
         return {k: (b._obs(), b.reward, b.done, False, b._logits_info(logp, entropy)) for k, b in each}
 
+    def evaluate_order(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
+                                  "(search.improve takes one, or a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

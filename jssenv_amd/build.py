@@ -3,6 +3,7 @@
 * ``libjss_hip.so``  -- the MI355X kernels + C ABI (hipcc, gfx950 only);
 * ``libjss_beam_hip.so`` -- beam search's selection kernel (include/jss_beam.h), a library of its own with the same flags;
 * ``libjss_bound_hip.so`` -- the lower-bound kernel (include/jss_bound.h), a third HIP library built the same way;
+* ``libjss_order_hip.so`` -- the machine-order kernels (include/jss_order.h), a fourth HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -30,7 +31,10 @@ BEAM_OUT = os.path.join(_HERE, "libjss_beam_hip.so")
 _BOUND = os.path.join(_ROOT, "include", "jss_bound.h")       # ... and the makespan lower bounds (jss_bound)
 BOUND_SRC = os.path.join(_HERE, "csrc", "jss_bound.hip")     # (libjss_bound_hip.so: a library of its own as well)
 BOUND_OUT = os.path.join(_HERE, "libjss_bound_hip.so")
-_OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC))   # sources that libjss_hip.so does not include
+_ORDER = os.path.join(_ROOT, "include", "jss_order.h")       # ... and the evaluation of machine orders (jss_order_eval, jss_order_apply)
+ORDER_SRC = os.path.join(_HERE, "csrc", "jss_order.hip")     # (libjss_order_hip.so: a library of its own as well)
+ORDER_OUT = os.path.join(_HERE, "libjss_order_hip.so")
+_OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -48,10 +52,11 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
+        build_order_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -59,7 +64,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -68,7 +73,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -76,8 +81,17 @@ def build_bound_extension(force: bool = False) -> str:
     return BOUND_OUT
 
 
+def build_order_extension(force: bool = False) -> str:
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER]):
+        return ORDER_OUT
+    tmp = ORDER_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
+    os.replace(tmp, ORDER_OUT)
+    return ORDER_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -15,6 +15,7 @@
 #include "jss_keys.h"
 #include "jss_beam.h"
 #include "jss_bound.h"
+#include "jss_order.h"
 
 namespace jss_abi {
 
@@ -349,6 +350,33 @@ inline int check_bound(const JssDesc *d, const JssState *s, const JssBound *b) {
     if (rc) return rc;
     if (!d->rem || !b->lower_bound) return JSS_E_NULL;
     if (b->n < 0 || (!b->parent && b->n != d->batch)) return JSS_E_SHAPE;
+    return 0;
+}
+
+// ---- machine orders (include/jss_order.h) ----------------------------------------------------------------------------
+// What libjss_order_hip.so keeps in LDS for one candidate: the op row and the start / tail row (int32), the machines' sequences
+// and the pair marks (uint16) over the entries of a [jmax][mmax] row rounded up to a multiple of 8, and five 64-word blocks.
+constexpr long long kOrderLdsLimit = 64 * 1024;
+inline long long order_entries8(int jmax, int mmax) { return ((long long)jmax * mmax + 7) / 8 * 8; }
+inline long long order_lds_bytes(int jmax, int mmax) { return 12 * order_entries8(jmax, mmax) + 5 * 64 * 4; }
+
+// jss_order_eval (libjss_order_hip.so and the twin): the batch as jss_lookahead checks it
+inline int check_order_eval(const JssDesc *d, const JssState *s, const JssOrder *o) {
+    if (!d || !s || !o) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!o->rank || !o->makespan) return JSS_E_NULL;
+    if (o->n < 0 || (!o->parent && o->n != d->batch)) return JSS_E_SHAPE;
+    if (!o->swap_a != !o->swap_b) return JSS_E_SHAPE;
+    const int pairs = (o->pair_a != nullptr) + (o->pair_b != nullptr) + (o->n_pairs != nullptr);
+    if ((pairs != 0 && pairs != 3) || (pairs == 3 && o->pair_cap < 1)) return JSS_E_SHAPE;
+    return order_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+inline int check_order_apply(const JssOrderApply *a) {
+    if (!a || !a->rank || !a->cur || !a->makespan || !a->pair_a || !a->pair_b || !a->improved) return JSS_E_NULL;
+    if (a->batch < 0 || a->jmax < 1 || a->jmax > JSS_MAX_JOBS || a->mmax < 1 || a->mmax > JSS_MAX_MACHINES || a->pair_cap < 1)
+        return JSS_E_SHAPE;
     return 0;
 }
 

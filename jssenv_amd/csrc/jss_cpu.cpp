@@ -1430,4 +1430,121 @@ int jss_bound(const JssDesc *desc, const JssState *state, const JssBound *bound,
     return 0;
 }
 
+// include/jss_order.h: the definition, candidate by candidate.  The machines' orders by a sort of (rank, flat index), the starts
+// by a worklist over the operations whose job and machine predecessors are placed (what is left over when it runs dry sits on
+// a cycle), the tails by a walk over the placing order backwards.
+int jss_order_eval(const JssDesc *desc, const JssState *state, const JssOrder *order, void *) {
+    if (const int rc = check_order_eval(desc, state, order)) return rc;
+    const JssDesc d = *desc;
+    const JssOrder o = *order;
+    const int region = d.jmax * d.mmax;
+    auto one = [&](int c) {
+        const int parent = o.parent ? o.parent[c] : c;
+        const int sa = o.swap_a ? o.swap_a[c] : -1, sb = o.swap_b ? o.swap_b[c] : -1;
+        if (parent < 0 || parent >= d.batch) return void(o.makespan[c] = -1);
+        const int32_t *ec = state->env_const + (size_t)parent * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return void(o.makespan[c] = -1);
+        auto real = [&](int e) { return e >= 0 && e < region && e / d.mmax < J && e % d.mmax < M; };
+        const bool swaps = sa != -1 || sb != -1;
+        if (swaps && (!real(sa) || !real(sb))) return void(o.makespan[c] = -1);
+        const int32_t *rank = o.rank + (size_t)parent * region, *ops = d.ops + (size_t)tab * region;
+        std::vector<int32_t> r(region, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) {
+                const int e = j * d.mmax + k;
+                if (rank[e] < 0) return void(o.makespan[c] = -1);
+                r[e] = rank[e];
+            }
+        if (swaps) std::swap(r[sa], r[sb]);
+        // the machines' orders, one behind the other: seq[first[m] .. first[m + 1])
+        std::vector<int> seq((size_t)J * M), first(JSS_MAX_MACHINES + 1, 0), pos(region, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) first[((ops[j * d.mmax + k] >> 16) & 63) + 1] += 1;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) first[m + 1] += first[m];
+        {
+            std::vector<int> fill(first.begin(), first.end() - 1);
+            for (int j = 0; j < J; ++j)
+                for (int k = 0; k < M; ++k) seq[fill[(ops[j * d.mmax + k] >> 16) & 63]++] = j * d.mmax + k;
+        }
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            std::sort(seq.begin() + first[m], seq.begin() + first[m + 1], [&](int x, int y) { return r[x] != r[y] ? r[x] < r[y] : x < y; });
+        for (int i = 0; i < (int)seq.size(); ++i) pos[seq[i]] = i;
+        auto mach_of = [&](int e) { return (ops[e] >> 16) & 63; };
+        auto dur_of = [&](int e) { return ops[e] & 0xFFFF; };
+        // forward
+        std::vector<int32_t> start(region, -1), tail(region, -1);
+        std::vector<int> placed;
+        placed.reserve(seq.size());
+        auto can_start = [&](int e) {
+            if (start[e] >= 0) return false;
+            if (e % d.mmax > 0 && start[e - 1] < 0) return false;
+            return pos[e] == first[mach_of(e)] || start[seq[pos[e] - 1]] >= 0;
+        };
+        std::vector<int> work;
+        for (int j = 0; j < J; ++j)
+            if (can_start(j * d.mmax)) work.push_back(j * d.mmax);
+        int makespan = 0;
+        while (!work.empty()) {
+            const int e = work.back();
+            work.pop_back();
+            if (!can_start(e)) continue;
+            int st = e % d.mmax > 0 ? start[e - 1] + dur_of(e - 1) : 0;
+            if (pos[e] > first[mach_of(e)]) st = std::max(st, start[seq[pos[e] - 1]] + dur_of(seq[pos[e] - 1]));
+            start[e] = st;
+            makespan = std::max(makespan, st + dur_of(e));
+            placed.push_back(e);
+            if (e % d.mmax + 1 < M) work.push_back(e + 1);
+            if (pos[e] + 1 < first[mach_of(e) + 1]) work.push_back(seq[pos[e] + 1]);
+        }
+        if (placed.size() != seq.size()) return void(o.makespan[c] = -2);
+        o.makespan[c] = makespan;
+        if (o.start) std::copy(start.begin(), start.end(), o.start + (size_t)c * region);
+        if (!o.tail && !o.pair_a) return;
+        // backward: every successor of an operation was placed behind it
+        for (int i = (int)placed.size() - 1; i >= 0; --i) {
+            const int e = placed[i];
+            int tl = e % d.mmax + 1 < M ? dur_of(e + 1) + tail[e + 1] : 0;
+            if (pos[e] + 1 < first[mach_of(e) + 1]) tl = std::max(tl, dur_of(seq[pos[e] + 1]) + tail[seq[pos[e] + 1]]);
+            tail[e] = tl;
+        }
+        if (o.tail) std::copy(tail.begin(), tail.end(), o.tail + (size_t)c * region);
+        if (!o.pair_a) return;
+        auto critical = [&](int e) { return start[e] + dur_of(e) + tail[e] == makespan; };
+        int32_t *pa = o.pair_a + (size_t)c * o.pair_cap, *pb = o.pair_b + (size_t)c * o.pair_cap;
+        int found = 0;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            for (int i = first[m]; i + 1 < first[m + 1]; ++i) {
+                const int u = seq[i], v = seq[i + 1];
+                if (u / d.mmax == v / d.mmax || !critical(u) || !critical(v) || start[v] != start[u] + dur_of(u)) continue;
+                if (found < o.pair_cap) pa[found] = u, pb[found] = v;
+                ++found;
+            }
+        for (int i = found; i < o.pair_cap; ++i) pa[i] = -1, pb[i] = -1;
+        o.n_pairs[c] = found;
+    };
+    parallel_for(o.n, d.threads, one);
+    return 0;
+}
+
+int jss_order_apply(const JssOrderApply *apply, void *) {
+    if (const int rc = check_order_apply(apply)) return rc;
+    const JssOrderApply a = *apply;
+    const int region = a.jmax * a.mmax;
+    auto one = [&](int i) {
+        const int32_t *mk = a.makespan + (size_t)i * a.pair_cap, *pa = a.pair_a + (size_t)i * a.pair_cap, *pb = a.pair_b + (size_t)i * a.pair_cap;
+        int at = -1;
+        for (int k = 0; k < a.pair_cap; ++k)
+            if (mk[k] >= 0 && pa[k] >= 0 && pa[k] < region && pb[k] >= 0 && pb[k] < region && (at < 0 || mk[k] < mk[at])) at = k;
+        a.improved[i] = 0;
+        if (at < 0 || mk[at] >= a.cur[i]) return;
+        int32_t *row = a.rank + (size_t)i * region;
+        std::swap(row[pa[at]], row[pb[at]]);
+        a.cur[i] = mk[at];
+        a.improved[i] = 1;
+    };
+    parallel_for(a.batch, 0, one);
+    return 0;
+}
+
 }  // extern "C"

@@ -789,6 +789,86 @@ class BatchedJssEnv:
             out += (est.reshape(shape + (self.jmax, self.mmax)),)
         return out[0] if len(out) == 1 else out
 
+    # -- the exact schedule of a machine order (jss_order_eval, include/jss_order.h) ---------------------------------------------
+    def evaluate_order(self, rank=None, parents=None, swaps=None, start: bool = False, tail: bool = False, pairs: Optional[int] = None):
+        """The semi-active schedule of an order of the operations on each machine, and its makespan (include/jss_order.h defines
+        it; integers, the same bits on every backend).  ``rank`` is int32 ``(B, jmax, mmax)``, one row per env: machine m works
+        through its operations ascending by (rank, job, operation index); ``None`` takes the env's own ``solution`` -- the start
+        times of a finished schedule are such a rank.  Only the instance tables are read; the batch is not touched.
+
+        No further arguments: every env's row, int32 ``(B,)`` makespans.  ``parents`` (n,): candidate c evaluates env
+        ``parents[c]``'s row.  ``swaps=(a, b)`` (two (n,) sequences, or one (n, 2) array) exchanges the ranks of the flat
+        operation indices ``j * mmax + k`` first, in the kernel -- the rank tensor is neither copied nor written; (-1, -1) is no
+        swap.  -1 marks what is refused (a parent out of range or never reset, a negative rank of a real operation, e.g. an
+        unfinished env's solution, a swap index that is out of range, names padding or stands alone), -2 an order that is cyclic
+        with the job chains.
+        ``start=True`` adds the start times ``(n, jmax, mmax)``, ``tail=True`` the tails (the longest path from an operation's
+        end to the end of the schedule), ``pairs=cap`` the neighbourhood ``pair_a, pair_b (n, cap)`` and ``n_pairs (n,)``:
+        consecutive critical operations of different jobs on a machine without a gap, by machine and position, -1 behind the
+        count, which also counts what did not fit.  Padding and the rows of refused or cyclic candidates are -1 (``n_pairs``
+        too).  The result is then the tuple ``(makespan[, start][, tail][, pair_a, pair_b, n_pairs])``.  Arrays of the env's
+        backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before evaluate_order()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError("evaluate_order does not run while a step session is open on this env: close() it first")
+        from .search import order_library
+        be = self.backend
+        lib = order_library(be)
+        B = self.batch
+        if pairs is not None and int(pairs) < 1:
+            raise ValueError("evaluate_order: pairs is the capacity of the pair lists, at least 1")
+        with be.on_device():
+            rk = self.solution if rank is None else be.as_device(rank, "int32")
+            if tuple(rk.shape) != (B, self.jmax, self.mmax):
+                raise ValueError(f"evaluate_order: rank must have shape {(B, self.jmax, self.mmax)}, got {tuple(rk.shape)}")
+            keep = [rk]
+            own = lambda x: x if getattr(be, "torch", None) is not None else x.copy()   # noqa: E731  (as_device keeps ONE array alive)
+            par = None
+            if parents is not None:
+                par = own(be.as_device(parents, "int32"))
+                if par.ndim != 1:
+                    raise ValueError("evaluate_order: parents must be 1-d")
+            n = B if par is None else int(par.shape[0])
+            sa = sb = None
+            if swaps is not None:
+                if isinstance(swaps, (tuple, list)) and len(swaps) == 2 and np.ndim(swaps[0]) == 1:
+                    sa, sb = own(be.as_device(swaps[0], "int32")), own(be.as_device(swaps[1], "int32"))
+                else:
+                    both = be.as_device(swaps, "int32")
+                    if both.ndim != 2 or both.shape[1] != 2:
+                        raise ValueError("evaluate_order: swaps is (a, b) with two 1-d sequences, or an (n, 2) array")
+                    sa, sb = own(be.as_device(both[:, 0], "int32")), own(be.as_device(both[:, 1], "int32"))
+                if tuple(sa.shape) != (n,) or tuple(sb.shape) != (n,):
+                    raise ValueError(f"evaluate_order: swaps must name one pair per candidate ({n})")
+            keep += [par, sa, sb]
+
+            def minus_one(shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            mk = minus_one((n,))
+            st = minus_one((n, self.jmax, self.mmax)) if start else None
+            tl = minus_one((n, self.jmax, self.mmax)) if tail else None
+            cap = 0 if pairs is None else int(pairs)
+            pa, pb, npairs = (minus_one((n, cap)), minus_one((n, cap)), minus_one((n,))) if cap else (None, None, None)
+            if n:
+                p = be.ptr
+                arg = _abi.JssOrder(n, cap, p(rk), p(par), p(sa), p(sb), p(mk), p(st), p(tl), p(pa), p(pb), p(npairs))
+                rc = lib.jss_order_eval(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_order_eval")
+            self._order_keep = keep                            # alive until the launch has read them
+        out = (mk,)
+        if start:
+            out += (st,)
+        if tail:
+            out += (tl,)
+        if cap:
+            out += (pa, pb, npairs)
+        return out[0] if len(out) == 1 else out
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

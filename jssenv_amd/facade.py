@@ -320,6 +320,24 @@ class JssEnv(gymnasium_base("Env")):
         b = self._b
         return int(b.backend.numpy(b.lower_bound())[0])
 
+    def evaluate_order(self, rank=None, swap=None, start: bool = False, tail: bool = False, pairs=None):
+        """The B = 1 form of ``BatchedJssEnv.evaluate_order`` (include/jss_order.h): the makespan of the semi-active schedule of
+        the machine order ``rank`` (J x M or jmax x mmax; None: this env's finished ``solution``), optionally with the ranks of
+        the two flat operation indices ``swap=(a, b)`` exchanged first; -1 refused, -2 cyclic.  ``start`` / ``tail`` / ``pairs``
+        add the host arrays of the one row: ``(makespan[, start][, tail][, pair_a, pair_b, n_pairs])``."""
+        b = self._b
+        if rank is not None:
+            r = np.full((1, b.jmax, b.mmax), -1, np.int32)
+            rank = np.asarray(rank)
+            r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
+            rank = r
+        swaps = None if swap is None else ([int(swap[0])], [int(swap[1])])
+        out = b.evaluate_order(rank, None, swaps, start, tail, pairs)
+        if not isinstance(out, tuple):
+            return int(b.backend.numpy(out)[0])
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return (int(host[0]),) + tuple(int(x) if x.ndim == 0 else x for x in host[1:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

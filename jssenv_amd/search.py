@@ -8,6 +8,10 @@ those calls alone: ``beam_select_reference`` is the selection written in NumPy, 
 
 Also here: ``lower_bound_reference``, the NumPy mirror of ``jss_bound`` (include/jss_bound.h: makespan lower bounds of states and
 of candidate moves, per-operation earliest starts), and ``bound_library``; ``BatchedJssEnv.lower_bound`` is the call.
+
+And the evaluation of machine orders (include/jss_order.h): ``order_eval_reference``, the NumPy mirror of ``jss_order_eval``,
+``order_library``, and ``improve``, steepest descent over swaps of adjacent critical operations -- three launches per iteration,
+defined by ``BatchedJssEnv.evaluate_order``, an arg-min and a swap (tests/order_cases.py writes that loop out).
 """
 from __future__ import annotations
 
@@ -243,6 +247,113 @@ def lower_bound_reference(env_header, env_const, solution, ops, rem, parents=Non
     return lower, jobb, est
 
 
+# ---- machine orders (include/jss_order.h), in NumPy ---------------------------------------------------------------------------
+def order_library(backend):
+    """The library of ``backend`` that exports include/jss_order.h: ``backend.order_lib`` (HipBackend: libjss_order_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
+    lib = getattr(backend, "order_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.ORDER_SYMBOLS):
+            raise RuntimeError("evaluate_order: the backend's library does not export include/jss_order.h")
+        _abi.bind_order(lib)
+    return lib
+
+
+def order_eval_reference(env_const, ops, rank, parents=None, swap_a=None, swap_b=None, pair_cap=None, fill=-1):
+    """include/jss_order.h's jss_order_eval on host arrays, written from the header's definition, one candidate after the
+    other: the machines' orders by a lexicographic sort, the starts over the operations in an order in which every predecessor
+    comes first (what cannot be so ordered is cyclic), the tails over the same order backwards, the pairs by a walk along the
+    machines.  ``env_const`` (B, 12), ``ops`` (n_tables, jmax, mmax), ``rank`` (B, jmax, mmax); ``parents``, ``swap_a``,
+    ``swap_b`` (n,) or None.  Returns ``(makespan, start, tail, pair_a, pair_b, n_pairs)``: int32 (n,), (n, jmax, mmax) twice,
+    (n, pair_cap) twice and (n,) -- the pair outputs None unless ``pair_cap`` is given.  Rows of refused (-1) and cyclic (-2)
+    candidates hold ``fill`` in every output but the makespan."""
+    rank = np.asarray(rank, dtype=np.int64)
+    B, jmax, mmax = rank.shape
+    const = np.asarray(env_const, dtype=np.int64).reshape(B, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    region = jmax * mmax
+    parents = np.arange(B) if parents is None else np.asarray(parents, dtype=np.int64).reshape(-1)
+    n = parents.size
+    swap_a = np.full(n, -1, np.int64) if swap_a is None else np.asarray(swap_a, dtype=np.int64).reshape(-1)
+    swap_b = np.full(n, -1, np.int64) if swap_b is None else np.asarray(swap_b, dtype=np.int64).reshape(-1)
+    makespan = np.full(n, -1, np.int32)
+    start = np.full((n, jmax, mmax), fill, np.int32)
+    tail = np.full((n, jmax, mmax), fill, np.int32)
+    cap = None if pair_cap is None else int(pair_cap)
+    pair_a = pair_b = n_pairs = None
+    if cap is not None:
+        pair_a, pair_b, n_pairs = np.full((n, cap), fill, np.int32), np.full((n, cap), fill, np.int32), np.full(n, fill, np.int32)
+    for c in range(n):
+        i, a, b = int(parents[c]), int(swap_a[c]), int(swap_b[c])
+        if not 0 <= i < B:
+            continue
+        J, M, tab = (int(x) for x in const[i, [_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE]])
+        if J < 1:
+            continue
+        real = np.zeros((jmax, mmax), bool)
+        real[:J, :M] = True
+        flat_real = real.reshape(-1)
+        r = rank[i].reshape(-1).copy()
+        if (r[flat_real] < 0).any():
+            continue
+        if (a, b) != (-1, -1):
+            if not (0 <= a < region and 0 <= b < region and flat_real[a] and flat_real[b]):
+                continue
+            r[a], r[b] = r[b], r[a]
+        mach = (ops[tab].reshape(-1) >> 16) & 63
+        dur = ops[tab].reshape(-1) & 0xFFFF
+        real_ops = np.flatnonzero(flat_real)
+        before = np.full(region, -1)                                  # the operation before / behind on the machine
+        behind = np.full(region, -1)
+        orders = []
+        for m in range(_abi.MAX_MACHINES):
+            on = real_ops[mach[real_ops] == m]
+            on = on[np.lexsort((on, r[on]))]                          # by (rank, flat index) = (rank, j, k)
+            orders.append(on)
+            before[on[1:]], behind[on[:-1]] = on[:-1], on[1:]
+        waits = np.zeros(region, np.int64)                            # predecessors not placed yet
+        waits[real_ops] = (real_ops % mmax > 0).astype(np.int64) + (before[real_ops] >= 0)
+        st = np.zeros(region, np.int64)
+        todo = [int(e) for e in real_ops if waits[e] == 0]
+        placed = []
+        while todo:
+            e = todo.pop()
+            placed.append(e)
+            end = st[e] + dur[e]
+            for nxt in ((e + 1) if e % mmax + 1 < M else -1, int(behind[e])):
+                if nxt >= 0:
+                    st[nxt] = max(st[nxt], end)
+                    waits[nxt] -= 1
+                    if waits[nxt] == 0:
+                        todo.append(nxt)
+        if len(placed) != real_ops.size:
+            makespan[c] = -2
+            continue
+        mk = int((st + dur)[real_ops].max())
+        tl = np.zeros(region, np.int64)
+        for e in reversed(placed):
+            job_next = e + 1 if e % mmax + 1 < M else -1
+            for nxt in (job_next, int(behind[e])):
+                if nxt >= 0:
+                    tl[e] = max(tl[e], dur[nxt] + tl[nxt])
+        makespan[c] = mk
+        start[c] = np.where(flat_real, st, -1).reshape(jmax, mmax)
+        tail[c] = np.where(flat_real, tl, -1).reshape(jmax, mmax)
+        if cap is not None:
+            critical = st + dur + tl == mk
+            found = []
+            for on in orders:
+                for u, v in zip(on[:-1], on[1:]):
+                    if u // mmax != v // mmax and critical[u] and critical[v] and st[v] == st[u] + dur[u]:
+                        found.append((int(u), int(v)))
+            n_pairs[c] = len(found)
+            pair_a[c], pair_b[c] = -1, -1
+            for k, (u, v) in enumerate(found[:cap]):
+                pair_a[c, k], pair_b[c, k] = u, v
+    return makespan, start, tail, pair_a, pair_b, n_pairs
+
+
 # ---- the driver ------------------------------------------------------------------------------------------------------------
 @dataclass
 class BeamResult:
@@ -368,3 +479,102 @@ def _walk_back(src, action, slot):
             out.append(int(action[lv, slot]))
         slot = int(src[lv, slot])
     return out[::-1]
+
+
+# ---- descent over swaps of adjacent critical operations -----------------------------------------------------------------------
+@dataclass
+class ImproveResult:
+    """What ``improve`` returns, host arrays: ``makespan_before`` and ``makespan`` (B,), the final ``rank`` and the ``start``
+    times of its schedule (B, jmax, mmax; a negative makespan and -1 rows: the env's schedule could not be evaluated).
+    ``iterations``: those in which some env improved; ``evaluations``: swap candidates evaluated, over all envs and all
+    iterations up to and including the one that improved nothing; ``truncated``: the (env, iteration) whose neighbourhood did
+    not fit ``pair_cap``; ``history`` (iterations run, B): the makespans at the start of every iteration; ``env`` the batch."""
+    makespan_before: np.ndarray
+    makespan: np.ndarray
+    rank: np.ndarray
+    start: np.ndarray
+    iterations: int
+    evaluations: int
+    truncated: int
+    history: Optional[np.ndarray] = None
+    env: Optional[BatchedJssEnv] = None
+
+
+def improve(env_or_instances, kind="SPT", max_iter=None, pair_cap=128, check_every=8, device=None, _backend=None):
+    """Steepest descent over swaps of adjacent critical operations, every env of a batch at once.  ``env_or_instances``: an
+    instance (a name, a path, an ``Instance``) or a list of them -- one env each, reset and rolled out with the rule ``kind``
+    -- or a ``BatchedJssEnv``: one that was never reset is reset and rolled out, one whose envs are all done is taken as it is.
+
+    The rank starts as the solution (start times order every machine).  An iteration is three launches and nothing else:
+    ``jss_order_eval`` of the B rows with the pairs out; ``jss_order_eval`` of the B * ``pair_cap`` candidates, candidate
+    (i, k) being env i's row with the ranks of its k-th pair exchanged in the kernel; ``jss_order_apply``, which takes each env's
+    lowest (makespan, k) if that is lower than the env's current makespan.  Every ``check_every`` iterations the driver reads
+    the window's ``improved`` flags and stops after the first iteration in which no env improved (or after ``max_iter``);
+    iterations run past that one change nothing, so the result does not depend on ``check_every``.  No acceptance of equal or
+    worse neighbours, no tabu list, no restarts: the schedule ends in a local optimum of this neighbourhood."""
+    cap, check_every = int(pair_cap), int(check_every)
+    if cap < 1 or check_every < 1:
+        raise ValueError("improve: pair_cap and check_every must be >= 1")
+    if isinstance(env_or_instances, BatchedJssEnv):
+        env = env_or_instances
+        fresh = not env._is_reset
+    elif isinstance(env_or_instances, PackedBatch) or type(env_or_instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError("improve takes instances or a BatchedJssEnv")
+    else:
+        one = isinstance(env_or_instances, (str, os.PathLike, Instance))
+        names = [env_or_instances] if one else list(env_or_instances)
+        if not names:
+            raise ValueError("improve: need at least one instance")
+        kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+        if len(names) == 1:
+            env = BatchedJssEnv(names[0], batch=1, **kw)
+        else:
+            env = BatchedJssEnv(names, batch=len(names), table_of_env=np.arange(len(names)), order="interleaved", **kw)
+        fresh = True
+    be = env.backend
+    if fresh:
+        env.reset()
+        env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False)
+    elif not (np.asarray(be.numpy(env.done)) != 0).all():
+        raise ValueError("improve: the batch is neither fresh nor done -- finish its episodes first")
+    lib = order_library(be)
+    B, region = env.batch, env.jmax * env.mmax
+    p = be.ptr
+    with be.on_device():
+        rank = env.solution.clone() if hasattr(env.solution, "clone") else np.array(env.solution, copy=True)
+        cur = env.evaluate_order(rank)
+        before = np.asarray(be.numpy(cur)).astype(np.int32)
+        cand_parent = be.from_numpy(np.repeat(np.arange(B, dtype=np.int32), cap))
+        pa, pb = be.zeros((B, cap), "int32"), be.zeros((B, cap), "int32")
+        cand_mk = be.zeros((B * cap,), "int32")
+        win_mk, win_pairs, win_improved = (be.zeros((check_every, B), "int32") for _ in range(3))
+        rows = _abi.JssOrder(B, cap, p(rank), None, None, None, None, None, None, p(pa), p(pb), None)
+        cands = _abi.JssOrder(B * cap, 0, p(rank), p(cand_parent), p(pa), p(pb), p(cand_mk), None, None, None, None, None)
+        apply = _abi.JssOrderApply(B, env.jmax, env.mmax, cap, p(rank), p(cur), p(cand_mk), p(pa), p(pb), None)
+        desc, state, stream = C.byref(env._desc), C.byref(env._state), be.stream()
+        history, iterations, evaluations, truncated, ran, finished = [], 0, 0, 0, 0, False
+        while not finished and (max_iter is None or ran < int(max_iter)):
+            n_win = check_every if max_iter is None else min(check_every, int(max_iter) - ran)
+            for i in range(n_win):
+                rows.makespan, rows.n_pairs, apply.improved = p(win_mk[i]), p(win_pairs[i]), p(win_improved[i])
+                for rc, what in ((lib.jss_order_eval(desc, state, C.byref(rows), stream), "jss_order_eval"),
+                                 (lib.jss_order_eval(desc, state, C.byref(cands), stream), "jss_order_eval"),
+                                 (lib.jss_order_apply(C.byref(apply), stream), "jss_order_apply")):
+                    if rc:
+                        _abi.check(be.lib, rc, what)
+            improved = np.asarray(be.numpy(win_improved))[:n_win]       # the one host round trip of the window
+            idle = np.flatnonzero(~(improved != 0).any(axis=1))
+            used = int(idle[0]) + 1 if idle.size else n_win          # up to and including the iteration that improved nothing
+            finished = bool(idle.size)
+            pairs = np.asarray(be.numpy(win_pairs))[:used].astype(np.int64)
+            history.append(np.asarray(be.numpy(win_mk))[:used].copy())
+            iterations += used - (1 if finished else 0)
+            evaluations += int(np.minimum(np.maximum(pairs, 0), cap).sum())
+            truncated += int((pairs > cap).sum())
+            ran += used
+        makespan, start = env.evaluate_order(rank, start=True)
+        res = ImproveResult(makespan_before=before, makespan=np.asarray(be.numpy(makespan)).astype(np.int32),
+                            rank=np.asarray(be.numpy(rank)).copy(), start=np.asarray(be.numpy(start)).copy(), iterations=iterations,
+                            evaluations=evaluations, truncated=truncated,
+                            history=np.concatenate(history) if history else np.zeros((0, B), np.int32), env=env)
+    return res

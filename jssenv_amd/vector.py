@@ -100,6 +100,10 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
     def makespan(self):
         return self._out(self.env.makespan)
 
+    def evaluate_order(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
+                                  "(search.improve takes one, or a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
