@@ -106,6 +106,13 @@ BOUND_SYMBOLS = ("jss_bound",)
 ORDER_VERSION = 1
 ORDER_SYMBOLS = ("jss_order_eval", "jss_order_apply")
 
+# include/jss_tabu.h: the companion header of tabu search over machine orders (its own version).  The HIP library exports it
+# from a fifth library, libjss_tabu_hip.so; the twin from libjss_cpu.so.
+TABU_VERSION = 1
+TABU_SYMBOLS = ("jss_tabu_search",)
+TABU_NI = 4                       # info row: stop, moves, best_move, evaluations
+TABU_MAX_ITERS, TABU_MAX_TENURE = 65536, 64
+
 _p = C.c_void_p
 
 
@@ -182,6 +189,11 @@ class JssOrder(C.Structure):         # include/jss_order.h
 class JssOrderApply(C.Structure):    # include/jss_order.h
     _fields_ = [("batch", C.c_int32), ("jmax", C.c_int32), ("mmax", C.c_int32), ("pair_cap", C.c_int32), ("rank", _p), ("cur", _p),
                 ("makespan", _p), ("pair_a", _p), ("pair_b", _p), ("improved", _p)]
+
+
+class JssTabu(C.Structure):          # include/jss_tabu.h
+    _fields_ = [("iters", C.c_int32), ("tenure", C.c_int32), ("rank", _p), ("tenure_of", _p), ("target", _p),
+                ("best_makespan", _p), ("best_rank", _p), ("last_rank", _p), ("info", _p), ("trace", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -312,6 +324,16 @@ def bind_order(lib):
     lib.jss_order_eval.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssOrder), _p]
     lib.jss_order_apply.restype = C.c_int
     lib.jss_order_apply.argtypes = [C.POINTER(JssOrderApply), _p]
+    return lib
+
+
+def bind_tabu(lib):
+    """Attach the prototype of include/jss_tabu.h; raises AttributeError naming the first missing symbol."""
+    for name in TABU_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_tabu_search.restype = C.c_int
+    lib.jss_tabu_search.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssTabu), _p]
     return lib
 
 

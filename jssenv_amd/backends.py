@@ -48,6 +48,7 @@ class HipBackend:
         self._beam_lib = None
         self._bound_lib = None
         self._order_lib = None
+        self._tabu_lib = None
 
     @property
     def beam_lib(self):
@@ -78,6 +79,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
             self._order_lib = _abi.bind_order(C.CDLL(path))
         return self._order_lib
+
+    @property
+    def tabu_lib(self):
+        """libjss_tabu_hip.so (include/jss_tabu.h), loaded on first use; a missing library is an error."""
+        if self._tabu_lib is None:
+            path = _abi.library_path("libjss_tabu_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            self._tabu_lib = _abi.bind_tabu(C.CDLL(path))
+        return self._tabu_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -281,6 +292,11 @@ class CpuBackend:
     def order_lib(self):
         """the library that exports include/jss_order.h: the twin itself"""
         return _abi.bind_order(self.lib)
+
+    @property
+    def tabu_lib(self):
+        """the library that exports include/jss_tabu.h: the twin itself"""
+        return _abi.bind_tabu(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

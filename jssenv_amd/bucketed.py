@@ -214,6 +214,10 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
                                   "(search.improve takes one, or a list of instances)")
 
+    def tabu(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu on a BatchedJssEnv "
+                                  "(search.tabu_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

@@ -16,6 +16,7 @@
 #include "jss_beam.h"
 #include "jss_bound.h"
 #include "jss_order.h"
+#include "jss_tabu.h"
 
 namespace jss_abi {
 
@@ -378,6 +379,21 @@ inline int check_order_apply(const JssOrderApply *a) {
     if (a->batch < 0 || a->jmax < 1 || a->jmax > JSS_MAX_JOBS || a->mmax < 1 || a->mmax > JSS_MAX_MACHINES || a->pair_cap < 1)
         return JSS_E_SHAPE;
     return 0;
+}
+
+// ---- tabu search (include/jss_tabu.h) --------------------------------------------------------------------------------
+// What libjss_tabu_hip.so keeps in LDS for one walker, for the whole walk: the same rows as one candidate of jss_order_eval.
+inline long long tabu_lds_bytes(int jmax, int mmax) { return order_lds_bytes(jmax, mmax); }
+
+// jss_tabu_search (libjss_tabu_hip.so and the twin): the batch as jss_order_eval checks it
+inline int check_tabu_search(const JssDesc *d, const JssState *s, const JssTabu *t) {
+    if (!d || !s || !t) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!t->rank || !t->best_makespan || !t->best_rank) return JSS_E_NULL;
+    if (t->iters < 0 || t->iters > 65536) return JSS_E_SHAPE;
+    if (!t->tenure_of && (t->tenure < 0 || t->tenure > 64)) return JSS_E_SHAPE;
+    return tabu_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

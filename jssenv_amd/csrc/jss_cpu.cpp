@@ -1547,4 +1547,155 @@ int jss_order_apply(const JssOrderApply *apply, void *) {
     return 0;
 }
 
+// include/jss_tabu.h: the definition, walker by walker.  The machines' orders are sorted once, as jss_order_eval sorts them;
+// after that a move is the exchange of two neighbouring entries of seq[].  The current order is timed forwards and backwards (the
+// pairs), every neighbour forwards only, by a worklist over the jobs whose next operation stands at its machine's cursor.
+int jss_tabu_search(const JssDesc *desc, const JssState *state, const JssTabu *tabu, void *) {
+    if (const int rc = check_tabu_search(desc, state, tabu)) return rc;
+    const JssDesc d = *desc;
+    const JssTabu t = *tabu;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int i) {
+        auto refuse = [&](int code) {
+            t.best_makespan[i] = code;
+            if (t.info) {
+                int32_t *row = t.info + (size_t)i * JSS_TABU_NI;
+                row[0] = code, row[1] = row[2] = row[3] = 0;
+            }
+        };
+        const int32_t *ec = state->env_const + (size_t)i * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return refuse(-1);
+        const int L = t.tenure_of ? t.tenure_of[i] : t.tenure;
+        if (L < 0 || L > 64) return refuse(-1);
+        const int32_t *rank = t.rank + (size_t)i * region, *ops = d.ops + (size_t)tab * region;
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k)
+                if (rank[j * mmax + k] < 0) return refuse(-1);
+        const int total = J * M;
+        auto mach_of = [&](int e) { return (ops[e] >> 16) & 63; };
+        auto dur_of = [&](int e) { return ops[e] & 0xFFFF; };
+        std::vector<int> seq((size_t)total), first(JSS_MAX_MACHINES + 1, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) first[mach_of(j * mmax + k) + 1] += 1;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) first[m + 1] += first[m];
+        {
+            std::vector<int> fill(first.begin(), first.end() - 1);
+            for (int j = 0; j < J; ++j)
+                for (int k = 0; k < M; ++k) seq[fill[mach_of(j * mmax + k)]++] = j * mmax + k;
+        }
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            std::sort(seq.begin() + first[m], seq.begin() + first[m + 1],
+                      [&](int x, int y) { return rank[x] != rank[y] ? rank[x] < rank[y] : x < y; });
+        // forward: the makespan of seq[], -1 when it has no schedule; the starts and the placing order where asked for
+        std::vector<int> cursor(JSS_MAX_MACHINES), release(JSS_MAX_MACHINES), next_k(J), job_end(J), work, placed, pos(region, 0);
+        std::vector<int32_t> start(region, -1), tail(region, -1);
+        work.reserve(2 * (size_t)total + J), placed.reserve(total);
+        auto forward = [&](bool keep) {
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m) cursor[m] = first[m], release[m] = 0;
+            std::fill(next_k.begin(), next_k.end(), 0), std::fill(job_end.begin(), job_end.end(), 0);
+            work.clear();
+            if (keep) placed.clear();
+            for (int j = J - 1; j >= 0; --j) work.push_back(j);
+            int done = 0, makespan = 0;
+            while (!work.empty()) {
+                const int j = work.back();
+                work.pop_back();
+                while (next_k[j] < M) {                                 // (a job runs on while its operations head their machines)
+                    const int e = j * mmax + next_k[j], m = mach_of(e);
+                    if (seq[cursor[m]] != e) break;
+                    const int st = std::max(job_end[j], release[m]);
+                    if (keep) start[e] = st, placed.push_back(e);
+                    job_end[j] = release[m] = st + dur_of(e);
+                    makespan = std::max(makespan, job_end[j]);
+                    next_k[j] += 1, cursor[m] += 1, done += 1;
+                    if (cursor[m] < first[m + 1]) {                     // the machine's new head: its job may be waiting for it
+                        const int h = seq[cursor[m]];
+                        if (h / mmax != j && next_k[h / mmax] == h % mmax) work.push_back(h / mmax);
+                    }
+                }
+            }
+            return done == total ? makespan : -1;
+        };
+        int cur = forward(true);
+        if (cur < 0) return refuse(-2);
+        int best = cur, moves = 0, best_move = 0, stop = 0;
+        int evaluations = 0;                                            // (at most 65536 * 5351)
+        auto write_positions = [&](int32_t *out) {
+            std::fill(out, out + region, -1);
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at < first[m + 1]; ++at) out[seq[at]] = at - first[m];
+        };
+        write_positions(t.best_rank + (size_t)i * region);
+        int32_t *trace = t.trace ? t.trace + (size_t)i * t.iters : nullptr;
+        const int32_t *target = t.target ? t.target + i : nullptr;
+        int list_key[64], list_move[64];                                // move s sits in entry (s - 1) % 64
+        std::fill(list_key, list_key + 64, -1), std::fill(list_move, list_move + 64, 0);
+        std::vector<int> pairs;
+        if (target && best <= *target) stop = 2;
+        for (int mv = 1; mv <= t.iters && stop == 0; ++mv) {
+            if (mv > 1) forward(true);                                  // the starts of the order the last move left
+            for (int at = 0; at < total; ++at) pos[seq[at]] = at;
+            for (int x = total - 1; x >= 0; --x) {                      // every successor of an operation was placed behind it
+                const int e = placed[x], m = mach_of(e);
+                int tl = e % mmax + 1 < M ? dur_of(e + 1) + tail[e + 1] : 0;
+                if (pos[e] + 1 < first[m + 1]) tl = std::max(tl, dur_of(seq[pos[e] + 1]) + tail[seq[pos[e] + 1]]);
+                tail[e] = tl;
+            }
+            auto critical = [&](int e) { return start[e] + dur_of(e) + tail[e] == cur; };
+            pairs.clear();
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at + 1 < first[m + 1]; ++at) {
+                    const int u = seq[at], v = seq[at + 1];
+                    if (u / mmax != v / mmax && critical(u) && critical(v) && start[v] == start[u] + dur_of(u)) pairs.push_back(at);
+                }
+            evaluations += (int)pairs.size();
+            const int lo = std::max(1, mv - L);                         // the moves lo ... mv - 1 are the last L
+            int take = -1, take_mk = 0, forced = -1, forced_mk = 0, forced_age = 0;
+            for (int at : pairs) {
+                std::swap(seq[at], seq[at + 1]);
+                const int mk = forward(false);
+                std::swap(seq[at], seq[at + 1]);
+                if (mk < 0) continue;
+                const int a = seq[at], b = seq[at + 1], key = std::min(a, b) << 16 | std::max(a, b);
+                int recent = 0;                                         // the latest of the last L moves that made this pair, or 0
+                for (int l = 0; l < 64; ++l)
+                    if (list_key[l] == key && list_move[l] >= lo) recent = std::max(recent, list_move[l]);
+                if (recent == 0 || mk < best) {
+                    if (take < 0 || mk < take_mk) take = at, take_mk = mk;
+                } else if (forced < 0 || recent < forced_age) {
+                    forced = at, forced_mk = mk, forced_age = recent;
+                }
+            }
+            if (take < 0) take = forced, take_mk = forced_mk;
+            if (take < 0) {
+                stop = 1;
+                break;
+            }
+            {
+                const int a = seq[take], b = seq[take + 1];
+                list_key[(mv - 1) & 63] = std::min(a, b) << 16 | std::max(a, b), list_move[(mv - 1) & 63] = mv;
+            }
+            std::swap(seq[take], seq[take + 1]);
+            cur = take_mk, moves = mv;
+            if (trace) trace[mv - 1] = cur;
+            if (cur < best) {
+                best = cur, best_move = mv;
+                write_positions(t.best_rank + (size_t)i * region);
+            }
+            if (target && best <= *target) stop = 2;
+        }
+        t.best_makespan[i] = best;
+        if (t.last_rank) write_positions(t.last_rank + (size_t)i * region);
+        if (trace)
+            for (int x = moves; x < t.iters; ++x) trace[x] = -1;
+        if (t.info) {
+            int32_t *row = t.info + (size_t)i * JSS_TABU_NI;
+            row[0] = stop, row[1] = moves, row[2] = best_move, row[3] = evaluations;
+        }
+    };
+    parallel_for<true>(d.batch, d.threads, one);
+    return 0;
+}
+
 }  // extern "C"

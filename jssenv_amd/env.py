@@ -869,6 +869,78 @@ class BatchedJssEnv:
             out += (pa, pb, npairs)
         return out[0] if len(out) == 1 else out
 
+    # -- tabu search over machine orders (jss_tabu_search, include/jss_tabu.h) ---------------------------------------------------
+    def tabu(self, rank=None, iters: int = 100, tenure=8, target=None, trace: bool = False, last: bool = False):
+        """One tabu walk per env, the whole walk in one launch (include/jss_tabu.h defines it; integers, the same bits on every
+        backend).  ``rank`` is a machine order as ``evaluate_order`` takes it, int32 ``(B, jmax, mmax)``; ``None`` takes the env's
+        own ``solution``.  A move exchanges two adjacent critical operations of different jobs on a machine: every such
+        neighbour of the current order is timed, the best one that is not tabu -- or that beats the best schedule of the walk --
+        is taken, also when it is worse, and its pair is tabu for the next ``tenure`` moves (an int in [0, 64], or one per env,
+        ``(B,)``).  At most ``iters`` moves (up to 65536); ``target`` (None, an int or ``(B,)``) ends a walk once its best
+        makespan is <= the target.  Only the instance tables are read; the batch is not touched.
+
+        Returns ``(best_makespan, best_rank, info[, trace][, last_rank])``: ``best_makespan`` (B,) with -1 for a refused row
+        (as ``evaluate_order`` refuses it, or a tenure outside [0, 64]) and -2 for a cyclic start; ``best_rank``
+        (B, jmax, mmax), the best order as positions on the machines, -1 in the padding and in refused or cyclic rows; ``info``
+        (B, 4): stop (0 ``iters`` moves made, 1 no neighbour left: optimal, 2 target reached, -1 / -2), moves, the move that found
+        the best, neighbours evaluated; ``trace`` (B, iters): the makespan after every move, -1 behind the last; ``last_rank``:
+        the order the walk ended in.  Arrays of the env's backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before tabu()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError("tabu does not run while a step session is open on this env: close() it first")
+        from .search import tabu_library
+        be = self.backend
+        lib = tabu_library(be)
+        B, iters = self.batch, int(iters)
+        if not 0 <= iters <= _abi.TABU_MAX_ITERS:
+            raise ValueError(f"tabu: iters must be in [0, {_abi.TABU_MAX_ITERS}]")
+        with be.on_device():
+            rk = self.solution if rank is None else be.as_device(rank, "int32")
+            if tuple(rk.shape) != (B, self.jmax, self.mmax):
+                raise ValueError(f"tabu: rank must have shape {(B, self.jmax, self.mmax)}, got {tuple(rk.shape)}")
+            own = lambda x: x if getattr(be, "torch", None) is not None else x.copy()   # noqa: E731  (as_device keeps ONE array alive)
+
+            def per_env(x, name):
+                if x is None or np.ndim(x) == 0:
+                    return None
+                x = own(be.as_device(x, "int32"))
+                if tuple(x.shape) != (B,):
+                    raise ValueError(f"tabu: {name} must be an int or have shape {(B,)}")
+                return x
+
+            tenure_of = per_env(tenure, "tenure")
+            if tenure_of is None and not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
+                raise ValueError(f"tabu: tenure must be in [0, {_abi.TABU_MAX_TENURE}]")
+            tgt = per_env(target, "target")
+            if tgt is None and target is not None:
+                tgt = be.zeros((B,), "int32")
+                tgt += int(target)
+
+            def minus_one(shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            mk, best = minus_one((B,)), minus_one((B, self.jmax, self.mmax))
+            info = be.zeros((B, _abi.TABU_NI), "int32")
+            tr = minus_one((B, iters)) if trace else None
+            lr = minus_one((B, self.jmax, self.mmax)) if last else None
+            if B:
+                p = be.ptr
+                arg = _abi.JssTabu(iters, 0 if tenure_of is not None else int(tenure), p(rk), p(tenure_of), p(tgt), p(mk), p(best),
+                                   p(lr), p(info), p(tr))
+                rc = lib.jss_tabu_search(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_tabu_search")
+            self._tabu_keep = [rk, tenure_of, tgt]             # alive until the launch has read them
+        out = (mk, best, info)
+        if trace:
+            out += (tr,)
+        if last:
+            out += (lr,)
+        return out
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

@@ -12,6 +12,11 @@ of candidate moves, per-operation earliest starts), and ``bound_library``; ``Bat
 And the evaluation of machine orders (include/jss_order.h): ``order_eval_reference``, the NumPy mirror of ``jss_order_eval``,
 ``order_library``, and ``improve``, steepest descent over swaps of adjacent critical operations -- three launches per iteration,
 defined by ``BatchedJssEnv.evaluate_order``, an arg-min and a swap (tests/order_cases.py writes that loop out).
+
+And tabu search over that neighbourhood (include/jss_tabu.h): ``tabu_reference``, the NumPy mirror of ``jss_tabu_search`` on top of
+``order_eval_reference``, ``tabu_library``, and ``tabu_search``, the driver: many walkers per instance, whole walks in one launch
+(``BatchedJssEnv.tabu``), defined by ``reset``, ``lower_bound``, ``rollout``, ``tabu`` and ``evaluate_order`` alone
+(tests/tabu_cases.py writes that loop out).
 """
 from __future__ import annotations
 
@@ -578,3 +583,176 @@ def improve(env_or_instances, kind="SPT", max_iter=None, pair_cap=128, check_eve
                             evaluations=evaluations, truncated=truncated,
                             history=np.concatenate(history) if history else np.zeros((0, B), np.int32), env=env)
     return res
+
+
+# ---- tabu search over swaps of adjacent critical operations (include/jss_tabu.h) ---------------------------------------------------
+def tabu_library(backend):
+    """The library of ``backend`` that exports include/jss_tabu.h: ``backend.tabu_lib`` (HipBackend: libjss_tabu_hip.so, loaded
+    on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
+    lib = getattr(backend, "tabu_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.TABU_SYMBOLS):
+            raise RuntimeError("tabu: the backend's library does not export include/jss_tabu.h")
+        _abi.bind_tabu(lib)
+    return lib
+
+
+def tabu_reference(env_const, ops, rank, iters, tenure, target=None, fill=-1, log=None):
+    """include/jss_tabu.h's jss_tabu_search on host arrays, written from the header's definition on top of
+    ``order_eval_reference``, one walker after the other: the start's refusal, cycle and order, every move's pairs and every
+    neighbour's makespan are calls of that mirror.  ``env_const`` (B, 12), ``ops`` (n_tables, jmax, mmax), ``rank``
+    (B, jmax, mmax); ``tenure`` an int or (B,); ``target`` None, an int or (B,).  Returns ``(best_makespan, best_rank,
+    last_rank, info, trace)``: int32 (B,), (B, jmax, mmax) twice, (B, 4), (B, iters).  The rows of refused (-1) and cyclic (-2)
+    walkers hold ``fill`` in both ranks and in the trace.  ``log``: a list that receives ``(walker, move, "aspired" | "forced")``
+    for every move that took a tabu neighbour: by aspiration, or because no neighbour was admissible."""
+    rank = np.asarray(rank, dtype=np.int64)
+    B, jmax, mmax = rank.shape
+    region, iters = jmax * mmax, int(iters)
+    const = np.asarray(env_const, dtype=np.int64).reshape(B, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    tenure = np.broadcast_to(np.asarray(tenure, dtype=np.int64), (B,))
+    target = None if target is None else np.broadcast_to(np.asarray(target, dtype=np.int64), (B,))
+    best_mk = np.full(B, -1, np.int32)
+    best_rank = np.full((B, jmax, mmax), fill, np.int32)
+    last_rank = np.full((B, jmax, mmax), fill, np.int32)
+    info = np.zeros((B, _abi.TABU_NI), np.int32)
+    trace = np.full((B, iters), fill, np.int32)
+    first = order_eval_reference(const, ops, rank)[0]
+    for i in range(B):
+        L = int(tenure[i])
+        if first[i] < 0 or not 0 <= L <= _abi.TABU_MAX_TENURE:
+            best_mk[i] = info[i, 0] = -1 if first[i] == -1 or not 0 <= L <= _abi.TABU_MAX_TENURE else -2
+            continue
+        J, M, tab = (int(x) for x in const[i, [_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE]])
+        one = const[i:i + 1]
+        mach = (ops[tab].reshape(-1) >> 16) & 63
+        real = np.zeros((jmax, mmax), bool)
+        real[:J, :M] = True
+        real_ops = np.flatnonzero(real.reshape(-1))
+        pos = np.full(region, -1, np.int64)                          # the order as positions: the operation's index on its machine
+        row = rank[i].reshape(-1)
+        for m in range(_abi.MAX_MACHINES):
+            on = real_ops[mach[real_ops] == m]
+            pos[on[np.lexsort((on, row[on]))]] = np.arange(on.size)
+        cur = best = int(first[i])
+        best_pos = pos.copy()
+        moves = best_move = evaluations = stop = 0
+        taken = []                                                    # (pair, move number) of every move
+        if target is not None and best <= target[i]:
+            stop = 2
+        for t in range(1, iters + 1):
+            if stop:
+                break
+            now = pos.reshape(1, jmax, mmax)
+            _, _, _, pa, pb, found = order_eval_reference(one, ops, now, pair_cap=region)
+            n = int(found[0])
+            evaluations += n
+            mk = order_eval_reference(one, ops, now, np.zeros(n, np.int64), pa[0, :n], pb[0, :n])[0] if n else np.zeros(0, np.int32)
+            usable = [k for k in range(n) if mk[k] >= 0]
+            if not usable:
+                stop = 1
+                break
+            pairs = [frozenset((int(pa[0, k]), int(pb[0, k]))) for k in range(n)]
+            recent = [max([s for pair, s in taken if pair == pairs[k] and s >= t - L], default=0) for k in range(n)]
+            admissible = [k for k in usable if recent[k] == 0 or mk[k] < best]
+            if admissible:
+                k = min(admissible, key=lambda k: (int(mk[k]), k))
+            else:
+                k = min(usable, key=lambda k: recent[k])
+            if log is not None and recent[k]:
+                log.append((i, t, "aspired" if admissible else "forced"))
+            a, b = int(pa[0, k]), int(pb[0, k])
+            pos[a], pos[b] = pos[b], pos[a]
+            cur = int(mk[k])
+            taken.append((pairs[k], t))
+            moves = t
+            trace[i, t - 1] = cur
+            if cur < best:
+                best, best_pos, best_move = cur, pos.copy(), t
+            if target is not None and best <= target[i]:
+                stop = 2
+        best_mk[i] = best
+        best_rank[i], last_rank[i] = best_pos.reshape(jmax, mmax), pos.reshape(jmax, mmax)
+        trace[i, moves:] = -1
+        info[i] = (stop, moves, best_move, evaluations)
+    return best_mk, best_rank, last_rank, info, trace
+
+
+@dataclass
+class TabuResult:
+    """What ``tabu_search`` returns, host arrays.  Per instance: ``makespan`` (G,), the lowest ``(best_makespan, walker)`` of its
+    group; ``walker`` (G,), that walker's index within the group; ``rank`` (G, jmax, mmax), its best order as positions; ``start``
+    (G, jmax, mmax), that order's start times; ``optimal`` (G,): the makespan is proven optimal (it reached the target, a lower
+    bound, or the walk found no critical machine arc).  ``best_makespan`` (S,) and ``info`` (S, 4) are the whole batch's,
+    ``target`` (S,) what the walks were given (None: nothing), ``tenure`` (S,) their tenures, ``env`` the batch."""
+    makespan: np.ndarray
+    walker: np.ndarray
+    rank: np.ndarray
+    start: np.ndarray
+    optimal: np.ndarray
+    best_makespan: np.ndarray
+    info: np.ndarray
+    target: Optional[np.ndarray] = None
+    tenure: Optional[np.ndarray] = None
+    env: Optional[BatchedJssEnv] = None
+
+
+def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), explore=0.1, seed=0, target="lower_bound",
+                device=None, _backend=None):
+    """Tabu search on one instance or on a list of them: one group of ``walkers`` envs per instance, all in one batch (laid out
+    like ``beam_search``'s groups), every walker's whole walk in ONE launch (``BatchedJssEnv.tabu``, include/jss_tabu.h).
+
+    The batch is reset and rolled out with the rule ``kind`` (``explore``: the share of random moves, so that the walkers of a
+    group start from different schedules); walker w of a group walks with tenure ``lo + w % (hi - lo + 1)`` for
+    ``tenure=(lo, hi)`` (an int: that tenure for all) for at most ``iters`` moves.  ``target="lower_bound"`` stops a walker
+    that reaches ``env.lower_bound()`` of the reset state -- a proof of optimality; ``None`` gives no target, an int or one
+    int per instance that target.  The result is defined by those public calls alone: ``reset``, ``lower_bound``, ``rollout``,
+    one ``tabu``, one ``evaluate_order``."""
+    W = int(walkers)
+    if W < 1:
+        raise ValueError("tabu_search: walkers must be >= 1")
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError("tabu_search takes instances (a name, a path, an Instance, or a list of them): call tabu on a "
+                                  "BatchedJssEnv for anything else")
+    one = isinstance(instances, (str, os.PathLike, Instance))
+    names = [instances] if one else list(instances)
+    G = len(names)
+    if G < 1:
+        raise ValueError("tabu_search: need at least one instance")
+    lo, hi = (int(tenure), int(tenure)) if np.ndim(tenure) == 0 else (int(tenure[0]), int(tenure[1]))
+    if not 0 <= lo <= hi <= _abi.TABU_MAX_TENURE:
+        raise ValueError(f"tabu_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}], low <= high")
+    S = G * W
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+    if G == 1:
+        env = BatchedJssEnv(names[0], batch=S, seed=int(seed or 0), **kw)
+    else:
+        env = BatchedJssEnv(names, batch=S, table_of_env=np.repeat(np.arange(G), W), order="interleaved", seed=int(seed or 0), **kw)
+    be = env.backend
+    env.reset()
+    if isinstance(target, str):
+        if target != "lower_bound":
+            raise ValueError("tabu_search: target is 'lower_bound', None, an int or one int per instance")
+        tgt = env.lower_bound()
+    elif target is None:
+        tgt = None
+    else:
+        tgt = np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), W)
+    env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False, explore=explore, seed=seed)
+    ten = (lo + (np.arange(S) % W) % (hi - lo + 1)).astype(np.int32)
+    best, best_rank, info = env.tabu(None, iters, ten, tgt)
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    mk, info = host(best).astype(np.int32), host(info).astype(np.int32)
+    tgt = None if tgt is None else host(tgt).astype(np.int32)
+    # the lowest (best_makespan, walker) of every group; a walker without a schedule counts as +inf
+    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
+    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
+    winner = (np.arange(G) * W + walker).astype(np.int32)
+    again, start = env.evaluate_order(best_rank, winner, start=True)
+    assert np.array_equal(host(again), mk[winner])
+    proven = info[:, 0] == 1
+    if tgt is not None:
+        proven |= (mk >= 0) & (mk <= tgt)
+    return TabuResult(makespan=mk[winner], walker=walker, rank=host(best_rank)[winner].copy(), start=host(start).copy(),
+                      optimal=proven[winner], best_makespan=mk, info=info, target=tgt, tenure=ten, env=env)

@@ -104,6 +104,10 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
                                   "(search.improve takes one, or a list of instances)")
 
+    def tabu(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu on a BatchedJssEnv "
+                                  "(search.tabu_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
