@@ -113,6 +113,13 @@ TABU_SYMBOLS = ("jss_tabu_search",)
 TABU_NI = 4                       # info row: stop, moves, best_move, evaluations
 TABU_MAX_ITERS, TABU_MAX_TENURE = 65536, 64
 
+# include/jss_block.h: the companion header of the block-insertion tabu walk (its own version).  The HIP library exports it from
+# a sixth library, libjss_block_hip.so; the twin from libjss_cpu.so.  iters, tenure and target range as in jss_tabu.h.
+BLOCK_VERSION = 1
+BLOCK_SYMBOLS = ("jss_block_search",)
+BLOCK_NI = 8                      # info row: stop, moves, best_move, evaluations, screened, far, hits, 0
+BLOCK_MAX_REACH = 65535
+
 _p = C.c_void_p
 
 
@@ -194,6 +201,11 @@ class JssOrderApply(C.Structure):    # include/jss_order.h
 class JssTabu(C.Structure):          # include/jss_tabu.h
     _fields_ = [("iters", C.c_int32), ("tenure", C.c_int32), ("rank", _p), ("tenure_of", _p), ("target", _p),
                 ("best_makespan", _p), ("best_rank", _p), ("last_rank", _p), ("info", _p), ("trace", _p)]
+
+
+class JssBlock(C.Structure):         # include/jss_block.h
+    _fields_ = [("iters", C.c_int32), ("tenure", C.c_int32), ("reach", C.c_int32), ("rank", _p), ("tenure_of", _p), ("target", _p),
+                ("best_makespan", _p), ("best_rank", _p), ("last_rank", _p), ("info", _p), ("trace", _p), ("move_log", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -334,6 +346,16 @@ def bind_tabu(lib):
             raise AttributeError(f"library does not export {name}")
     lib.jss_tabu_search.restype = C.c_int
     lib.jss_tabu_search.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssTabu), _p]
+    return lib
+
+
+def bind_block(lib):
+    """Attach the prototype of include/jss_block.h; raises AttributeError naming the first missing symbol."""
+    for name in BLOCK_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_block_search.restype = C.c_int
+    lib.jss_block_search.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBlock), _p]
     return lib
 
 

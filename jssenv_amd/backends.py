@@ -49,6 +49,7 @@ class HipBackend:
         self._bound_lib = None
         self._order_lib = None
         self._tabu_lib = None
+        self._block_lib = None
 
     @property
     def beam_lib(self):
@@ -89,6 +90,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
             self._tabu_lib = _abi.bind_tabu(C.CDLL(path))
         return self._tabu_lib
+
+    @property
+    def block_lib(self):
+        """libjss_block_hip.so (include/jss_block.h), loaded on first use; a missing library is an error."""
+        if self._block_lib is None:
+            path = _abi.library_path("libjss_block_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_block_extension)")
+            self._block_lib = _abi.bind_block(C.CDLL(path))
+        return self._block_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -297,6 +308,11 @@ class CpuBackend:
     def tabu_lib(self):
         """the library that exports include/jss_tabu.h: the twin itself"""
         return _abi.bind_tabu(self.lib)
+
+    @property
+    def block_lib(self):
+        """the library that exports include/jss_block.h: the twin itself"""
+        return _abi.bind_block(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

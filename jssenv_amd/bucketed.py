@@ -218,6 +218,10 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu on a BatchedJssEnv "
                                   "(search.tabu_search takes a list of instances)")
 
+    def tabu_blocks(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
+                                  "(search.tabu_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

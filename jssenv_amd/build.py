@@ -5,6 +5,7 @@
 * ``libjss_bound_hip.so`` -- the lower-bound kernel (include/jss_bound.h), a third HIP library built the same way;
 * ``libjss_order_hip.so`` -- the machine-order kernels (include/jss_order.h), a fourth HIP library built the same way;
 * ``libjss_tabu_hip.so`` -- the tabu-search kernel (include/jss_tabu.h), a fifth HIP library built the same way;
+* ``libjss_block_hip.so`` -- the block-insertion tabu kernel (include/jss_block.h), a sixth HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -38,8 +39,11 @@ ORDER_OUT = os.path.join(_HERE, "libjss_order_hip.so")
 _TABU = os.path.join(_ROOT, "include", "jss_tabu.h")         # ... and tabu search over machine orders (jss_tabu_search)
 TABU_SRC = os.path.join(_HERE, "csrc", "jss_tabu.hip")       # (libjss_tabu_hip.so: a library of its own as well)
 TABU_OUT = os.path.join(_HERE, "libjss_tabu_hip.so")
+_BLOCK = os.path.join(_ROOT, "include", "jss_block.h")       # ... and the tabu walk over block insertions (jss_block_search)
+BLOCK_SRC = os.path.join(_HERE, "csrc", "jss_block.hip")     # (libjss_block_hip.so: a library of its own as well)
+BLOCK_OUT = os.path.join(_HERE, "libjss_block_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
-                os.path.basename(TABU_SRC))                  # sources that libjss_hip.so does not include
+                os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -57,12 +61,13 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
         build_order_extension(force)
         build_tabu_extension(force)
+        build_block_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -70,7 +75,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -79,7 +84,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -88,7 +93,7 @@ def build_bound_extension(force: bool = False) -> str:
 
 
 def build_order_extension(force: bool = False) -> str:
-    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]):
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
         return ORDER_OUT
     tmp = ORDER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
@@ -97,7 +102,7 @@ def build_order_extension(force: bool = False) -> str:
 
 
 def build_tabu_extension(force: bool = False) -> str:
-    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]):
+    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
         return TABU_OUT
     tmp = TABU_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, TABU_SRC, "-o", tmp])
@@ -105,8 +110,17 @@ def build_tabu_extension(force: bool = False) -> str:
     return TABU_OUT
 
 
+def build_block_extension(force: bool = False) -> str:
+    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+        return BLOCK_OUT
+    tmp = BLOCK_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, BLOCK_SRC, "-o", tmp])
+    os.replace(tmp, BLOCK_OUT)
+    return BLOCK_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -17,6 +17,7 @@
 #include "jss_bound.h"
 #include "jss_order.h"
 #include "jss_tabu.h"
+#include "jss_block.h"
 
 namespace jss_abi {
 
@@ -394,6 +395,23 @@ inline int check_tabu_search(const JssDesc *d, const JssState *s, const JssTabu 
     if (t->iters < 0 || t->iters > 65536) return JSS_E_SHAPE;
     if (!t->tenure_of && (t->tenure < 0 || t->tenure > 64)) return JSS_E_SHAPE;
     return tabu_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// ---- block insertions (include/jss_block.h) ----------------------------------------------------------------------------
+// What libjss_block_hip.so keeps in LDS for one walker, for the whole walk: jss_order_eval's rows, and over the same entries
+// the tails (int32) and the list of the marked positions (uint16).
+inline long long block_lds_bytes(int jmax, int mmax) { return 18 * order_entries8(jmax, mmax) + 5 * 64 * 4; }
+
+// jss_block_search (libjss_block_hip.so and the twin): the batch as jss_order_eval checks it
+inline int check_block_search(const JssDesc *d, const JssState *s, const JssBlock *b) {
+    if (!d || !s || !b) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!b->rank || !b->best_makespan || !b->best_rank) return JSS_E_NULL;
+    if (b->iters < 0 || b->iters > 65536) return JSS_E_SHAPE;
+    if (!b->tenure_of && (b->tenure < 0 || b->tenure > 64)) return JSS_E_SHAPE;
+    if (b->reach < 0 || b->reach > 65535) return JSS_E_SHAPE;
+    return block_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

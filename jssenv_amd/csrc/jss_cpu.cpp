@@ -1698,4 +1698,196 @@ int jss_tabu_search(const JssDesc *desc, const JssState *state, const JssTabu *t
     return 0;
 }
 
+// include/jss_block.h: the definition, walker by walker.  The start is jss_tabu_search's; a move times the current order forwards
+// and backwards (starts, tails, marks), scores every candidate by one sweep along its stretch, rotates the stretch of the one it
+// takes and re-times that order, which is also the next move's forward pass.
+int jss_block_search(const JssDesc *desc, const JssState *state, const JssBlock *block, void *) {
+    if (const int rc = check_block_search(desc, state, block)) return rc;
+    const JssDesc d = *desc;
+    const JssBlock t = *block;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int i) {
+        auto refuse = [&](int code) {
+            t.best_makespan[i] = code;
+            if (t.info) {
+                int32_t *row = t.info + (size_t)i * JSS_BLOCK_NI;
+                std::fill(row, row + JSS_BLOCK_NI, 0);
+                row[0] = code;
+            }
+        };
+        const int32_t *ec = state->env_const + (size_t)i * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return refuse(-1);
+        const int L = t.tenure_of ? t.tenure_of[i] : t.tenure;
+        if (L < 0 || L > 64) return refuse(-1);
+        const int32_t *rank = t.rank + (size_t)i * region, *ops = d.ops + (size_t)tab * region;
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k)
+                if (rank[j * mmax + k] < 0) return refuse(-1);
+        const int total = J * M;
+        auto mach_of = [&](int e) { return (ops[e] >> 16) & 63; };
+        auto dur_of = [&](int e) { return ops[e] & 0xFFFF; };
+        std::vector<int> seq((size_t)total), first(JSS_MAX_MACHINES + 1, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) first[mach_of(j * mmax + k) + 1] += 1;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) first[m + 1] += first[m];
+        {
+            std::vector<int> fill(first.begin(), first.end() - 1);
+            for (int j = 0; j < J; ++j)
+                for (int k = 0; k < M; ++k) seq[fill[mach_of(j * mmax + k)]++] = j * mmax + k;
+        }
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            std::sort(seq.begin() + first[m], seq.begin() + first[m + 1],
+                      [&](int x, int y) { return rank[x] != rank[y] ? rank[x] < rank[y] : x < y; });
+        // forward: the makespan of seq[], -1 when it has no schedule; the starts and the placing order
+        std::vector<int> cursor(JSS_MAX_MACHINES), release(JSS_MAX_MACHINES), next_k(J), job_end(J), work, placed, pos(region, 0);
+        std::vector<int32_t> start(region, -1), tail(region, -1);
+        std::vector<char> mark((size_t)total + 1, 0);
+        work.reserve(2 * (size_t)total + J), placed.reserve(total);
+        auto forward = [&]() {
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m) cursor[m] = first[m], release[m] = 0;
+            std::fill(next_k.begin(), next_k.end(), 0), std::fill(job_end.begin(), job_end.end(), 0);
+            work.clear(), placed.clear();
+            for (int j = J - 1; j >= 0; --j) work.push_back(j);
+            int makespan = 0;
+            while (!work.empty()) {
+                const int j = work.back();
+                work.pop_back();
+                while (next_k[j] < M) {                                 // (a job runs on while its operations head their machines)
+                    const int e = j * mmax + next_k[j], m = mach_of(e);
+                    if (seq[cursor[m]] != e) break;
+                    const int st = std::max(job_end[j], release[m]);
+                    start[e] = st, placed.push_back(e);
+                    job_end[j] = release[m] = st + dur_of(e);
+                    makespan = std::max(makespan, job_end[j]);
+                    next_k[j] += 1, cursor[m] += 1;
+                    if (cursor[m] < first[m + 1]) {                     // the machine's new head: its job may be waiting for it
+                        const int h = seq[cursor[m]];
+                        if (h / mmax != j && next_k[h / mmax] == h % mmax) work.push_back(h / mmax);
+                    }
+                }
+            }
+            return (int)placed.size() == total ? makespan : -1;
+        };
+        int cur = forward();
+        if (cur < 0) return refuse(-2);
+        int best = cur, moves = 0, best_move = 0, stop = 0;
+        int evaluations = 0, screened = 0, far = 0, hits = 0;           // (at most 65536 * 2 * 3567 each)
+        auto write_positions = [&](int32_t *out) {
+            std::fill(out, out + region, -1);
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at < first[m + 1]; ++at) out[seq[at]] = at - first[m];
+        };
+        write_positions(t.best_rank + (size_t)i * region);
+        int32_t *trace = t.trace ? t.trace + (size_t)i * t.iters : nullptr;
+        int32_t *moved = t.move_log ? t.move_log + (size_t)i * t.iters * 2 : nullptr;
+        const int32_t *target = t.target ? t.target + i : nullptr;
+        int list_key[64], list_move[64];                                // move s sits in entry (s - 1) % 64
+        std::fill(list_key, list_key + 64, -1), std::fill(list_move, list_move + 64, 0);
+        if (target && best <= *target) stop = 2;
+        for (int mv = 1; mv <= t.iters && stop == 0; ++mv) {
+            for (int at = 0; at < total; ++at) pos[seq[at]] = at;
+            for (int x = total - 1; x >= 0; --x) {                      // every successor of an operation was placed behind it
+                const int e = placed[x], m = mach_of(e);
+                int tl = e % mmax + 1 < M ? dur_of(e + 1) + tail[e + 1] : 0;
+                if (pos[e] + 1 < first[m + 1]) tl = std::max(tl, dur_of(seq[pos[e] + 1]) + tail[seq[pos[e] + 1]]);
+                tail[e] = tl;
+            }
+            auto critical = [&](int e) { return start[e] + dur_of(e) + tail[e] == cur; };
+            auto E = [&](int e) { return start[e] + dur_of(e); };
+            auto Q = [&](int e) { return dur_of(e) + tail[e]; };
+            auto job_head = [&](int e) { return e % mmax > 0 ? E(e - 1) : 0; };
+            auto job_tail = [&](int e) { return e % mmax + 1 < M ? Q(e + 1) : 0; };
+            int marks = 0;
+            std::fill(mark.begin(), mark.end(), 0);
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at + 1 < first[m + 1]; ++at) {
+                    const int u = seq[at], v = seq[at + 1];
+                    if (u / mmax != v / mmax && critical(u) && critical(v) && start[v] == start[u] + dur_of(u)) mark[at] = 1, ++marks;
+                }
+            if (marks == 0) {
+                stop = 1;
+                break;
+            }
+            const int lo = std::max(1, mv - L);                         // the moves lo ... mv - 1 are the last L
+            // the choice so far: the stretch [from, to] of seq[], rotated to the left (F) or to the right (B)
+            int take = -1, take_to = 0, take_est = 0, take_back = 0, forced = -1, forced_to = 0, forced_est = 0, forced_back = 0, forced_age = 0;
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at + 1 < first[m + 1]; ++at) {
+                    if (!mark[at]) continue;
+                    int p0 = at, pL = at + 1;
+                    while (p0 > first[m] && mark[p0 - 1]) --p0;
+                    while (mark[pL]) ++pL;
+                    for (int back = 0; back <= (pL - p0 >= 2 ? 1 : 0); ++back) {
+                        const int from = back ? p0 : at, to = back ? at + 1 : pL;      // the stretch; x at `from` (F) or at `to` (B)
+                        const int x = seq[back ? to : from], y = seq[back ? from : to];
+                        if (t.reach > 0 && to - from > t.reach) continue;
+                        bool same_job = false;
+                        int head = from > first[m] ? E(seq[from - 1]) : 0, est = 0;
+                        const int behind = to + 1 < first[m + 1] ? Q(seq[to + 1]) : 0;
+                        for (int n = 0; n <= to - from; ++n) {           // the stretch in its new order
+                            const int e = back ? (n == 0 ? x : seq[from + n - 1]) : (n == to - from ? x : seq[from + n + 1]);
+                            if (e != x) same_job |= e / mmax == x / mmax;
+                            head = std::max(job_head(e), head) + dur_of(e);
+                            est = std::max(est, head + std::max(job_tail(e), n == to - from ? behind : 0));
+                        }
+                        const bool blocked = back ? x % mmax > 0 && !(E(y) > start[x - 1]) : x % mmax + 1 < M && !(Q(y) > tail[x + 1]);
+                        if (same_job || blocked) {
+                            ++screened;
+                            continue;
+                        }
+                        ++evaluations;
+                        const int key = std::min(x, y) << 16 | std::max(x, y);
+                        int recent = 0;                                 // the latest of the last L moves that made this pair, or 0
+                        for (int l = 0; l < 64; ++l)
+                            if (list_key[l] == key && list_move[l] >= lo) recent = std::max(recent, list_move[l]);
+                        if (recent == 0 || est < best) {
+                            if (take < 0 || est < take_est) take = from, take_to = to, take_est = est, take_back = back;
+                        } else if (forced < 0 || recent < forced_age) {
+                            forced = from, forced_to = to, forced_est = est, forced_back = back, forced_age = recent;
+                        }
+                    }
+                }
+            if (take < 0) take = forced, take_to = forced_to, take_est = forced_est, take_back = forced_back;
+            if (take < 0) {
+                stop = 3;
+                break;
+            }
+            const int x = seq[take_back ? take_to : take], y = seq[take_back ? take : take_to];
+            if (take_back) std::rotate(seq.begin() + take, seq.begin() + take_to, seq.begin() + take_to + 1);
+            else std::rotate(seq.begin() + take, seq.begin() + take + 1, seq.begin() + take_to + 1);
+            const int mk = forward();
+            if (mk < 0) {                                               // (unreachable: the screen) the move undone
+                if (take_back) std::rotate(seq.begin() + take, seq.begin() + take + 1, seq.begin() + take_to + 1);
+                else std::rotate(seq.begin() + take, seq.begin() + take_to, seq.begin() + take_to + 1);
+                stop = 4;
+                break;
+            }
+            list_key[(mv - 1) & 63] = std::min(x, y) << 16 | std::max(x, y), list_move[(mv - 1) & 63] = mv;
+            far += take_to - take >= 2, hits += take_est == mk;
+            cur = mk, moves = mv;
+            if (trace) trace[mv - 1] = cur;
+            if (moved) moved[2 * (mv - 1)] = x, moved[2 * (mv - 1) + 1] = y;
+            if (cur < best) {
+                best = cur, best_move = mv;
+                write_positions(t.best_rank + (size_t)i * region);
+            }
+            if (target && best <= *target) stop = 2;
+        }
+        t.best_makespan[i] = best;
+        if (t.last_rank) write_positions(t.last_rank + (size_t)i * region);
+        if (trace)
+            for (int x = moves; x < t.iters; ++x) trace[x] = -1;
+        if (moved)
+            for (int x = 2 * moves; x < 2 * t.iters; ++x) moved[x] = -1;
+        if (t.info) {
+            int32_t *row = t.info + (size_t)i * JSS_BLOCK_NI;
+            row[0] = stop, row[1] = moves, row[2] = best_move, row[3] = evaluations;
+            row[4] = screened, row[5] = far, row[6] = hits, row[7] = 0;
+        }
+    };
+    parallel_for<true>(d.batch, d.threads, one);
+    return 0;
+}
+
 }  // extern "C"

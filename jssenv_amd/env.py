@@ -941,6 +941,83 @@ class BatchedJssEnv:
             out += (lr,)
         return out
 
+    # -- tabu search over block insertions (jss_block_search, include/jss_block.h) ---------------------------------------------
+    def tabu_blocks(self, rank=None, iters: int = 100, tenure=8, target=None, reach: int = 0, trace: bool = False, last: bool = False,
+                    log: bool = False):
+        """One tabu walk per env over block insertions, the whole walk in one launch (include/jss_block.h defines it; integers,
+        the same bits on every backend).  ``rank``, ``iters``, ``tenure`` and ``target`` as in ``tabu``.  A move carries a
+        critical operation to the far end of its critical block on the machine (``reach`` > 0: at most that many places, so
+        ``reach=1`` leaves the swaps at the blocks' ends); every candidate is scored from the heads and tails of the current
+        schedule, the best estimate that is not tabu -- or that beats the best schedule of the walk -- is taken, and only that
+        order is re-timed exactly.  Only the instance tables are read; the batch is not touched.
+
+        Returns ``(best_makespan, best_rank, info[, trace][, last_rank][, move_log])``: as ``tabu`` returns them, with ``info``
+        (B, 8): stop (0 ``iters`` moves made, 1 no critical machine arc left: optimal, 2 target reached, 3 every candidate
+        screened, 4 never, -1 / -2), moves, the move that found the best, candidates scored, candidates screened (they could
+        close a cycle), moves of distance >= 2 taken, moves whose estimate was the exact makespan, 0; ``move_log``
+        (B, iters, 2): the flat indices of the operation moved and of the block end it passed, -1 behind the last move.
+        Arrays of the env's backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before tabu_blocks()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError("tabu_blocks does not run while a step session is open on this env: close() it first")
+        from .search import block_library
+        be = self.backend
+        lib = block_library(be)
+        B, iters, reach = self.batch, int(iters), int(reach)
+        if not 0 <= iters <= _abi.TABU_MAX_ITERS:
+            raise ValueError(f"tabu_blocks: iters must be in [0, {_abi.TABU_MAX_ITERS}]")
+        if not 0 <= reach <= _abi.BLOCK_MAX_REACH:
+            raise ValueError(f"tabu_blocks: reach must be in [0, {_abi.BLOCK_MAX_REACH}]")
+        with be.on_device():
+            rk = self.solution if rank is None else be.as_device(rank, "int32")
+            if tuple(rk.shape) != (B, self.jmax, self.mmax):
+                raise ValueError(f"tabu_blocks: rank must have shape {(B, self.jmax, self.mmax)}, got {tuple(rk.shape)}")
+            own = lambda x: x if getattr(be, "torch", None) is not None else x.copy()   # noqa: E731  (as_device keeps ONE array alive)
+
+            def per_env(x, name):
+                if x is None or np.ndim(x) == 0:
+                    return None
+                x = own(be.as_device(x, "int32"))
+                if tuple(x.shape) != (B,):
+                    raise ValueError(f"tabu_blocks: {name} must be an int or have shape {(B,)}")
+                return x
+
+            tenure_of = per_env(tenure, "tenure")
+            if tenure_of is None and not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
+                raise ValueError(f"tabu_blocks: tenure must be in [0, {_abi.TABU_MAX_TENURE}]")
+            tgt = per_env(target, "target")
+            if tgt is None and target is not None:
+                tgt = be.zeros((B,), "int32")
+                tgt += int(target)
+
+            def minus_one(shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            mk, best = minus_one((B,)), minus_one((B, self.jmax, self.mmax))
+            info = be.zeros((B, _abi.BLOCK_NI), "int32")
+            tr = minus_one((B, iters)) if trace else None
+            lr = minus_one((B, self.jmax, self.mmax)) if last else None
+            ml = minus_one((B, iters, 2)) if log else None
+            if B:
+                p = be.ptr
+                arg = _abi.JssBlock(iters, 0 if tenure_of is not None else int(tenure), reach, p(rk), p(tenure_of), p(tgt), p(mk),
+                                    p(best), p(lr), p(info), p(tr), p(ml))
+                rc = lib.jss_block_search(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_block_search")
+            self._block_keep = [rk, tenure_of, tgt]            # alive until the launch has read them
+        out = (mk, best, info)
+        if trace:
+            out += (tr,)
+        if last:
+            out += (lr,)
+        if log:
+            out += (ml,)
+        return out
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

@@ -352,6 +352,21 @@ class JssEnv(gymnasium_base("Env")):
         host = [np.asarray(b.backend.numpy(x))[0] for x in out]
         return (int(host[0]),) + tuple(host[1:])
 
+    def tabu_blocks(self, rank=None, iters: int = 100, tenure: int = 8, target=None, reach: int = 0, trace: bool = False,
+                    last: bool = False, log: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.tabu_blocks`` (include/jss_block.h): one tabu walk over block insertions of at most
+        ``iters`` moves from the machine order ``rank`` (J x M or jmax x mmax; None: this env's finished ``solution``).  Returns
+        ``(best_makespan, best_rank, info[, trace][, last_rank][, move_log])``: an int (-1 refused, -2 cyclic) and host arrays."""
+        b = self._b
+        if rank is not None:
+            r = np.full((1, b.jmax, b.mmax), -1, np.int32)
+            rank = np.asarray(rank)
+            r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
+            rank = r
+        out = b.tabu_blocks(rank, iters, int(tenure), None if target is None else int(target), reach, trace, last, log)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return (int(host[0]),) + tuple(host[1:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

@@ -17,6 +17,9 @@ And tabu search over that neighbourhood (include/jss_tabu.h): ``tabu_reference``
 ``order_eval_reference``, ``tabu_library``, and ``tabu_search``, the driver: many walkers per instance, whole walks in one launch
 (``BatchedJssEnv.tabu``), defined by ``reset``, ``lower_bound``, ``rollout``, ``tabu`` and ``evaluate_order`` alone
 (tests/tabu_cases.py writes that loop out).
+
+And the same walk over block insertions (include/jss_block.h): ``block_reference``, the NumPy mirror of ``jss_block_search``,
+``block_library``, and ``tabu_search(moves="block")`` through ``BatchedJssEnv.tabu_blocks``.
 """
 from __future__ import annotations
 
@@ -679,12 +682,177 @@ def tabu_reference(env_const, ops, rank, iters, tenure, target=None, fill=-1, lo
     return best_mk, best_rank, last_rank, info, trace
 
 
+# ---- tabu search over block insertions, scored by heads and tails (include/jss_block.h) -----------------------------------------
+def block_library(backend):
+    """The library of ``backend`` that exports include/jss_block.h: ``backend.block_lib`` (HipBackend: libjss_block_hip.so, loaded
+    on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
+    lib = getattr(backend, "block_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.BLOCK_SYMBOLS):
+            raise RuntimeError("tabu_blocks: the backend's library does not export include/jss_block.h")
+        _abi.bind_block(lib)
+    return lib
+
+
+def block_reference(env_const, ops, rank, iters, tenure, target=None, reach=0, fill=-1, log=None):
+    """include/jss_block.h's jss_block_search on host arrays, written from the header's definition on top of
+    ``order_eval_reference``, one walker after the other: the start's refusal, cycle and order, every move's starts and tails and
+    the re-timing of the move taken are calls of that mirror; blocks, candidates, screen, estimate and choice are written out
+    here.  Arguments as ``tabu_reference``'s, and ``reach``.  Returns ``(best_makespan, best_rank, last_rank, info, trace,
+    move_log)``: int32 (B,), (B, jmax, mmax) twice, (B, 8), (B, iters), (B, iters, 2).  The rows of refused (-1) and cyclic (-2)
+    walkers hold ``fill`` in both ranks, the trace and the move log.  ``log``: a list that receives ``(walker, move, event)``:
+    "F far" / "B far" for a move of distance >= 2 taken, "aspired" / "forced" for a tabu move taken, "job" / "successor" /
+    "predecessor" for a screened candidate (the first of the header's three conditions that holds), "reach" for a candidate that
+    ``reach`` cut."""
+    rank = np.asarray(rank, dtype=np.int64)
+    B, jmax, mmax = rank.shape
+    region, iters, reach = jmax * mmax, int(iters), int(reach)
+    const = np.asarray(env_const, dtype=np.int64).reshape(B, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    tenure = np.broadcast_to(np.asarray(tenure, dtype=np.int64), (B,))
+    target = None if target is None else np.broadcast_to(np.asarray(target, dtype=np.int64), (B,))
+    best_mk = np.full(B, -1, np.int32)
+    best_rank = np.full((B, jmax, mmax), fill, np.int32)
+    last_rank = np.full((B, jmax, mmax), fill, np.int32)
+    info = np.zeros((B, _abi.BLOCK_NI), np.int32)
+    trace = np.full((B, iters), fill, np.int32)
+    move_log = np.full((B, iters, 2), fill, np.int32)
+    note = (lambda *event: log.append(event)) if log is not None else (lambda *event: None)
+    first = order_eval_reference(const, ops, rank)[0]
+    for i in range(B):
+        L = int(tenure[i])
+        if first[i] < 0 or not 0 <= L <= _abi.TABU_MAX_TENURE:
+            best_mk[i] = info[i, 0] = -1 if first[i] == -1 or not 0 <= L <= _abi.TABU_MAX_TENURE else -2
+            continue
+        J, M, tab = (int(x) for x in const[i, [_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE]])
+        one = const[i:i + 1]
+        mach = (ops[tab].reshape(-1) >> 16) & 63
+        dur = ops[tab].reshape(-1) & 0xFFFF
+        real = np.zeros((jmax, mmax), bool)
+        real[:J, :M] = True
+        real_ops = np.flatnonzero(real.reshape(-1))
+        pos = np.full(region, -1, np.int64)                          # the order as positions: the operation's index on its machine
+        row = rank[i].reshape(-1)
+        for m in range(_abi.MAX_MACHINES):
+            on = real_ops[mach[real_ops] == m]
+            pos[on[np.lexsort((on, row[on]))]] = np.arange(on.size)
+        cur = best = int(first[i])
+        best_pos = pos.copy()
+        moves = best_move = evaluations = screened = far = hits = stop = 0
+        taken = []                                                    # (pair, move number) of every move
+        if target is not None and best <= target[i]:
+            stop = 2
+        for t in range(1, iters + 1):
+            if stop:
+                break
+            _, st, tl = order_eval_reference(one, ops, pos.reshape(1, jmax, mmax))[:3]
+            st, tl = st[0].reshape(-1).astype(np.int64), tl[0].reshape(-1).astype(np.int64)
+            E = lambda e: int(st[e] + dur[e]) if e >= 0 else 0       # noqa: E731  (a missing neighbour contributes 0)
+            Q = lambda e: int(dur[e] + tl[e]) if e >= 0 else 0       # noqa: E731
+            JP = lambda e: e - 1 if e % mmax > 0 else -1             # noqa: E731
+            JS = lambda e: e + 1 if e % mmax + 1 < M else -1         # noqa: E731
+            critical = st + dur + tl == cur
+            marks = 0
+            listed = []                                               # (estimate, x, y, the machine's new order, distance, kind)
+            for m in range(_abi.MAX_MACHINES):
+                on = real_ops[mach[real_ops] == m]
+                on = [int(e) for e in on[np.argsort(pos[on])]]
+                at_m = lambda a: on[a] if 0 <= a < len(on) else -1   # noqa: E731
+                marked = [a for a in range(len(on) - 1) if on[a] // mmax != on[a + 1] // mmax and critical[on[a]]
+                          and critical[on[a + 1]] and st[on[a + 1]] == st[on[a]] + dur[on[a]]]
+                marks += len(marked)
+                for at in marked:
+                    p0 = pL = at                                      # the block's marked positions are p0 ... pL - 1
+                    while p0 - 1 in marked:
+                        p0 -= 1
+                    while pL in marked:
+                        pL += 1
+                    cands = [("F", on[at], on[pL], on[at + 1:pL + 1], pL - at, at_m(at - 1), at_m(pL + 1))]
+                    if pL - p0 >= 2:
+                        cands.append(("B", on[at + 1], on[p0], on[p0:at + 1], at + 1 - p0, at_m(p0 - 1), at_m(at + 2)))
+                    for kind, x, y, jumped, dist, before, behind in cands:
+                        if reach > 0 and dist > reach:
+                            note(i, t, "reach")
+                            continue
+                        if any(w // mmax == x // mmax for w in jumped):
+                            screened += 1
+                            note(i, t, "job")
+                            continue
+                        if kind == "F" and JS(x) >= 0 and not Q(y) > tl[JS(x)]:
+                            screened += 1
+                            note(i, t, "successor")
+                            continue
+                        if kind == "B" and JP(x) >= 0 and not E(y) > st[JP(x)]:
+                            screened += 1
+                            note(i, t, "predecessor")
+                            continue
+                        evaluations += 1
+                        order = jumped + [x] if kind == "F" else [x] + jumped
+                        head, h = E(before), {}
+                        for e in order:
+                            h[e] = max(E(JP(e)), head)
+                            head = h[e] + int(dur[e])
+                        tail, est = Q(behind), 0
+                        for e in reversed(order):
+                            tail = int(dur[e]) + max(Q(JS(e)), tail)
+                            est = max(est, h[e] + tail)
+                        listed.append((est, x, y, jumped, dist, kind))
+            if not marks:
+                stop = 1
+                break
+            if not listed:
+                stop = 3
+                break
+            pairs = [frozenset((c[1], c[2])) for c in listed]
+            recent = [max([s for pair, s in taken if pair == pairs[k] and s >= t - L], default=0) for k in range(len(listed))]
+            admissible = [k for k in range(len(listed)) if recent[k] == 0 or listed[k][0] < best]
+            if admissible:
+                k = min(admissible, key=lambda k: (listed[k][0], k))
+            else:
+                k = min(range(len(listed)), key=lambda k: (recent[k], k))
+            est, x, y, jumped, dist, kind = listed[k]
+            old = pos.copy()
+            if kind == "F":
+                pos[x] = old[y]
+                pos[jumped] = old[jumped] - 1
+            else:
+                pos[x] = old[y]
+                pos[jumped] = old[jumped] + 1
+            mk = int(order_eval_reference(one, ops, pos.reshape(1, jmax, mmax))[0][0])
+            if mk < 0:                                                # (the screen makes this unreachable)
+                pos = old
+                stop = 4
+                break
+            if recent[k]:
+                note(i, t, "aspired" if admissible else "forced")
+            if dist >= 2:
+                far += 1
+                note(i, t, kind + " far")
+            hits += int(est == mk)
+            cur = mk
+            taken.append((pairs[k], t))
+            moves = t
+            trace[i, t - 1] = cur
+            move_log[i, t - 1] = (x, y)
+            if cur < best:
+                best, best_pos, best_move = cur, pos.copy(), t
+            if target is not None and best <= target[i]:
+                stop = 2
+        best_mk[i] = best
+        best_rank[i], last_rank[i] = best_pos.reshape(jmax, mmax), pos.reshape(jmax, mmax)
+        trace[i, moves:] = -1
+        move_log[i, moves:] = -1
+        info[i] = (stop, moves, best_move, evaluations, screened, far, hits, 0)
+    return best_mk, best_rank, last_rank, info, trace, move_log
+
+
 @dataclass
 class TabuResult:
     """What ``tabu_search`` returns, host arrays.  Per instance: ``makespan`` (G,), the lowest ``(best_makespan, walker)`` of its
     group; ``walker`` (G,), that walker's index within the group; ``rank`` (G, jmax, mmax), its best order as positions; ``start``
     (G, jmax, mmax), that order's start times; ``optimal`` (G,): the makespan is proven optimal (it reached the target, a lower
-    bound, or the walk found no critical machine arc).  ``best_makespan`` (S,) and ``info`` (S, 4) are the whole batch's,
+    bound, or the walk found no critical machine arc).  ``best_makespan`` (S,) and ``info`` (S, 4; S, 8 with ``moves="block"``) are the whole batch's,
     ``target`` (S,) what the walks were given (None: nothing), ``tenure`` (S,) their tenures, ``env`` the batch."""
     makespan: np.ndarray
     walker: np.ndarray
@@ -699,7 +867,7 @@ class TabuResult:
 
 
 def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), explore=0.1, seed=0, target="lower_bound",
-                device=None, _backend=None):
+                device=None, _backend=None, moves="swap", reach=0):
     """Tabu search on one instance or on a list of them: one group of ``walkers`` envs per instance, all in one batch (laid out
     like ``beam_search``'s groups), every walker's whole walk in ONE launch (``BatchedJssEnv.tabu``, include/jss_tabu.h).
 
@@ -708,10 +876,19 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     ``tenure=(lo, hi)`` (an int: that tenure for all) for at most ``iters`` moves.  ``target="lower_bound"`` stops a walker
     that reaches ``env.lower_bound()`` of the reset state -- a proof of optimality; ``None`` gives no target, an int or one
     int per instance that target.  The result is defined by those public calls alone: ``reset``, ``lower_bound``, ``rollout``,
-    one ``tabu``, one ``evaluate_order``."""
+    one ``tabu``, one ``evaluate_order``.
+
+    ``moves="block"`` walks over block insertions instead (``BatchedJssEnv.tabu_blocks``, include/jss_block.h: candidates scored
+    by head and tail estimates, one exact re-timing per move), ``reach`` its largest distance (0: no limit); the one ``tabu`` of
+    the definition is then one ``tabu_blocks``, ``info`` has its 8 columns, and stop 1 alone still proves optimality."""
     W = int(walkers)
     if W < 1:
         raise ValueError("tabu_search: walkers must be >= 1")
+    if moves not in ("swap", "block"):
+        raise ValueError("tabu_search: moves is 'swap' or 'block'")
+    reach = int(reach)
+    if not 0 <= reach <= _abi.BLOCK_MAX_REACH or (reach and moves == "swap"):
+        raise ValueError(f"tabu_search: reach must lie in [0, {_abi.BLOCK_MAX_REACH}], and is 0 with moves='swap'")
     if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
         raise NotImplementedError("tabu_search takes instances (a name, a path, an Instance, or a list of them): call tabu on a "
                                   "BatchedJssEnv for anything else")
@@ -741,7 +918,10 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
         tgt = np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), W)
     env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False, explore=explore, seed=seed)
     ten = (lo + (np.arange(S) % W) % (hi - lo + 1)).astype(np.int32)
-    best, best_rank, info = env.tabu(None, iters, ten, tgt)
+    if moves == "block":
+        best, best_rank, info = env.tabu_blocks(None, iters, ten, tgt, reach)
+    else:
+        best, best_rank, info = env.tabu(None, iters, ten, tgt)
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     mk, info = host(best).astype(np.int32), host(info).astype(np.int32)
     tgt = None if tgt is None else host(tgt).astype(np.int32)

@@ -108,6 +108,10 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu on a BatchedJssEnv "
                                   "(search.tabu_search takes a list of instances)")
 
+    def tabu_blocks(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
+                                  "(search.tabu_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
