@@ -120,6 +120,13 @@ BLOCK_SYMBOLS = ("jss_block_search",)
 BLOCK_NI = 8                      # info row: stop, moves, best_move, evaluations, screened, far, hits, 0
 BLOCK_MAX_REACH = 65535
 
+# include/jss_relink.h: the companion header of path relinking between machine orders (its own version).  The HIP library exports
+# it from a seventh library, libjss_relink_hip.so; the twin from libjss_cpu.so.
+RELINK_VERSION = 1
+RELINK_SYMBOLS = ("jss_relink_walk",)
+RELINK_NI = 8                     # info row: stop, moves, best_move, dist0, dist, candidates, fallbacks, retries
+RELINK_MAX_STEPS = 65536
+
 _p = C.c_void_p
 
 
@@ -206,6 +213,12 @@ class JssTabu(C.Structure):          # include/jss_tabu.h
 class JssBlock(C.Structure):         # include/jss_block.h
     _fields_ = [("iters", C.c_int32), ("tenure", C.c_int32), ("reach", C.c_int32), ("rank", _p), ("tenure_of", _p), ("target", _p),
                 ("best_makespan", _p), ("best_rank", _p), ("last_rank", _p), ("info", _p), ("trace", _p), ("move_log", _p)]
+
+
+class JssRelink(C.Structure):        # include/jss_relink.h
+    _fields_ = [("steps", C.c_int32), ("until", C.c_int32), ("margin", C.c_int32), ("rank", _p), ("guide", _p), ("until_of", _p),
+                ("best_makespan", _p), ("best_rank", _p), ("last_makespan", _p), ("last_rank", _p), ("info", _p), ("trace", _p),
+                ("move_log", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -356,6 +369,16 @@ def bind_block(lib):
             raise AttributeError(f"library does not export {name}")
     lib.jss_block_search.restype = C.c_int
     lib.jss_block_search.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBlock), _p]
+    return lib
+
+
+def bind_relink(lib):
+    """Attach the prototype of include/jss_relink.h; raises AttributeError naming the first missing symbol."""
+    for name in RELINK_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_relink_walk.restype = C.c_int
+    lib.jss_relink_walk.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssRelink), _p]
     return lib
 
 

@@ -50,6 +50,7 @@ class HipBackend:
         self._order_lib = None
         self._tabu_lib = None
         self._block_lib = None
+        self._relink_lib = None
 
     @property
     def beam_lib(self):
@@ -100,6 +101,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_block_extension)")
             self._block_lib = _abi.bind_block(C.CDLL(path))
         return self._block_lib
+
+    @property
+    def relink_lib(self):
+        """libjss_relink_hip.so (include/jss_relink.h), loaded on first use; a missing library is an error."""
+        if self._relink_lib is None:
+            path = _abi.library_path("libjss_relink_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_relink_extension)")
+            self._relink_lib = _abi.bind_relink(C.CDLL(path))
+        return self._relink_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -313,6 +324,11 @@ class CpuBackend:
     def block_lib(self):
         """the library that exports include/jss_block.h: the twin itself"""
         return _abi.bind_block(self.lib)
+
+    @property
+    def relink_lib(self):
+        """the library that exports include/jss_relink.h: the twin itself"""
+        return _abi.bind_relink(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -222,6 +222,14 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
                                   "(search.tabu_search takes a list of instances)")
 
+    def relink(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not relink machine orders: call relink on a BatchedJssEnv "
+                                  "(search.relink_search takes a list of instances)")
+
+    def order_distance(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
+                                  "(search.relink_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

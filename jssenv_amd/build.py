@@ -6,6 +6,7 @@
 * ``libjss_order_hip.so`` -- the machine-order kernels (include/jss_order.h), a fourth HIP library built the same way;
 * ``libjss_tabu_hip.so`` -- the tabu-search kernel (include/jss_tabu.h), a fifth HIP library built the same way;
 * ``libjss_block_hip.so`` -- the block-insertion tabu kernel (include/jss_block.h), a sixth HIP library built the same way;
+* ``libjss_relink_hip.so`` -- the path-relinking kernel (include/jss_relink.h), a seventh HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -42,8 +43,11 @@ TABU_OUT = os.path.join(_HERE, "libjss_tabu_hip.so")
 _BLOCK = os.path.join(_ROOT, "include", "jss_block.h")       # ... and the tabu walk over block insertions (jss_block_search)
 BLOCK_SRC = os.path.join(_HERE, "csrc", "jss_block.hip")     # (libjss_block_hip.so: a library of its own as well)
 BLOCK_OUT = os.path.join(_HERE, "libjss_block_hip.so")
+_RELINK = os.path.join(_ROOT, "include", "jss_relink.h")     # ... and path relinking between machine orders (jss_relink_walk)
+RELINK_SRC = os.path.join(_HERE, "csrc", "jss_relink.hip")   # (libjss_relink_hip.so: a library of its own as well)
+RELINK_OUT = os.path.join(_HERE, "libjss_relink_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
-                os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC))   # sources that libjss_hip.so does not include
+                os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -61,13 +65,14 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
         build_order_extension(force)
         build_tabu_extension(force)
         build_block_extension(force)
+        build_relink_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -75,7 +80,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -84,7 +89,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -93,7 +98,7 @@ def build_bound_extension(force: bool = False) -> str:
 
 
 def build_order_extension(force: bool = False) -> str:
-    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return ORDER_OUT
     tmp = ORDER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
@@ -102,7 +107,7 @@ def build_order_extension(force: bool = False) -> str:
 
 
 def build_tabu_extension(force: bool = False) -> str:
-    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return TABU_OUT
     tmp = TABU_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, TABU_SRC, "-o", tmp])
@@ -111,7 +116,7 @@ def build_tabu_extension(force: bool = False) -> str:
 
 
 def build_block_extension(force: bool = False) -> str:
-    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return BLOCK_OUT
     tmp = BLOCK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BLOCK_SRC, "-o", tmp])
@@ -119,8 +124,17 @@ def build_block_extension(force: bool = False) -> str:
     return BLOCK_OUT
 
 
+def build_relink_extension(force: bool = False) -> str:
+    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+        return RELINK_OUT
+    tmp = RELINK_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, RELINK_SRC, "-o", tmp])
+    os.replace(tmp, RELINK_OUT)
+    return RELINK_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

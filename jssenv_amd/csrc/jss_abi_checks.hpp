@@ -18,6 +18,7 @@
 #include "jss_order.h"
 #include "jss_tabu.h"
 #include "jss_block.h"
+#include "jss_relink.h"
 
 namespace jss_abi {
 
@@ -412,6 +413,22 @@ inline int check_block_search(const JssDesc *d, const JssState *s, const JssBloc
     if (!b->tenure_of && (b->tenure < 0 || b->tenure > 64)) return JSS_E_SHAPE;
     if (b->reach < 0 || b->reach > 65535) return JSS_E_SHAPE;
     return block_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// ---- path relinking (include/jss_relink.h) -------------------------------------------------------------------------------
+// What libjss_relink_hip.so keeps in LDS for one walker, for the whole walk: jss_order_eval's rows (with four blocks of one
+// word per machine), and over the same entries the tails (int32) and the guide positions (uint16).
+inline long long relink_lds_bytes(int jmax, int mmax) { return 18 * order_entries8(jmax, mmax) + 4 * 64 * 4; }
+
+// jss_relink_walk (libjss_relink_hip.so and the twin): the batch as jss_order_eval checks it
+inline int relink_check(const JssDesc *d, const JssState *s, const JssRelink *r) {
+    if (!d || !s || !r) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!r->rank || !r->guide || !r->best_makespan || !r->best_rank) return JSS_E_NULL;
+    if (r->steps < 0 || r->steps > 65536) return JSS_E_SHAPE;
+    if (r->until < 0 || r->margin < 0) return JSS_E_SHAPE;
+    return relink_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

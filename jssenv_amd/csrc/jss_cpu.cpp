@@ -1890,4 +1890,182 @@ int jss_block_search(const JssDesc *desc, const JssState *state, const JssBlock 
     return 0;
 }
 
+// include/jss_relink.h: the definition, walker by walker.  The start sorts and times both rows as jss_block_search sorts and
+// times its one; a move times the current order backwards (the forward pass is the last move's), lists the adjacent pairs the
+// guide has the other way round, screens and scores them, exchanges the two operations of the one it takes and re-times.
+int jss_relink_walk(const JssDesc *desc, const JssState *state, const JssRelink *relink, void *) {
+    if (const int rc = relink_check(desc, state, relink)) return rc;
+    const JssDesc d = *desc;
+    const JssRelink t = *relink;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int i) {
+        auto refuse = [&](int code) {
+            t.best_makespan[i] = code;
+            if (t.last_makespan) t.last_makespan[i] = code;
+            if (t.info) {
+                int32_t *row = t.info + (size_t)i * JSS_RELINK_NI;
+                std::fill(row, row + JSS_RELINK_NI, 0);
+                row[0] = code;
+            }
+        };
+        const int32_t *ec = state->env_const + (size_t)i * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return refuse(-1);
+        const int until = t.until_of ? t.until_of[i] : t.until;
+        if (until < 0) return refuse(-1);
+        const int32_t *rank = t.rank + (size_t)i * region, *guide = t.guide + (size_t)i * region, *ops = d.ops + (size_t)tab * region;
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k)
+                if (rank[j * mmax + k] < 0 || guide[j * mmax + k] < 0) return refuse(-1);
+        const int total = J * M;
+        auto mach_of = [&](int e) { return (ops[e] >> 16) & 63; };
+        auto dur_of = [&](int e) { return ops[e] & 0xFFFF; };
+        std::vector<int> seq((size_t)total), first(JSS_MAX_MACHINES + 1, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) first[mach_of(j * mmax + k) + 1] += 1;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) first[m + 1] += first[m];
+        auto sort_by = [&](const int32_t *key) {                        // seq[]: the machines' orders by (key, j, k)
+            std::vector<int> fill(first.begin(), first.end() - 1);
+            for (int j = 0; j < J; ++j)
+                for (int k = 0; k < M; ++k) seq[fill[mach_of(j * mmax + k)]++] = j * mmax + k;
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                std::sort(seq.begin() + first[m], seq.begin() + first[m + 1],
+                          [&](int x, int y) { return key[x] != key[y] ? key[x] < key[y] : x < y; });
+        };
+        // forward: the makespan of seq[], -1 when it has no schedule; the starts and the placing order (jss_block_search's)
+        std::vector<int> cursor(JSS_MAX_MACHINES), release(JSS_MAX_MACHINES), next_k(J), job_end(J), work, placed, pos(region, 0), g(region, 0);
+        std::vector<int32_t> start(region, -1), tail(region, -1);
+        work.reserve(2 * (size_t)total + J), placed.reserve(total);
+        auto forward = [&]() {
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m) cursor[m] = first[m], release[m] = 0;
+            std::fill(next_k.begin(), next_k.end(), 0), std::fill(job_end.begin(), job_end.end(), 0);
+            work.clear(), placed.clear();
+            for (int j = J - 1; j >= 0; --j) work.push_back(j);
+            int makespan = 0;
+            while (!work.empty()) {
+                const int j = work.back();
+                work.pop_back();
+                while (next_k[j] < M) {
+                    const int e = j * mmax + next_k[j], m = mach_of(e);
+                    if (seq[cursor[m]] != e) break;
+                    const int st = std::max(job_end[j], release[m]);
+                    start[e] = st, placed.push_back(e);
+                    job_end[j] = release[m] = st + dur_of(e);
+                    makespan = std::max(makespan, job_end[j]);
+                    next_k[j] += 1, cursor[m] += 1;
+                    if (cursor[m] < first[m + 1]) {
+                        const int h = seq[cursor[m]];
+                        if (h / mmax != j && next_k[h / mmax] == h % mmax) work.push_back(h / mmax);
+                    }
+                }
+            }
+            return (int)placed.size() == total ? makespan : -1;
+        };
+        sort_by(guide);
+        const bool guide_cyclic = forward() < 0;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            for (int at = first[m]; at < first[m + 1]; ++at) g[seq[at]] = at - first[m];
+        sort_by(rank);
+        int cur = forward();
+        if (cur < 0 || guide_cyclic) return refuse(-2);
+        int dist = 0;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            for (int a = first[m]; a < first[m + 1]; ++a)
+                for (int b = a + 1; b < first[m + 1]; ++b) dist += g[seq[a]] > g[seq[b]];
+        const int dist0 = dist;
+        int best = 0, moves = 0, best_move = -1, stop = 0, candidates = 0, fallbacks = 0, retries = 0;
+        auto write_positions = [&](int32_t *out) {
+            std::fill(out, out + region, -1);
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at < first[m + 1]; ++at) out[seq[at]] = at - first[m];
+        };
+        auto consider = [&](int mv) {                                   // the order after move mv as the best, where eligible
+            if (mv < t.margin || dist < t.margin || (best_move >= 0 && cur >= best)) return;
+            best = cur, best_move = mv;
+            write_positions(t.best_rank + (size_t)i * region);
+        };
+        auto stops = [&]() { return dist == 0 ? 1 : dist <= until ? 2 : 0; };
+        int32_t *trace = t.trace ? t.trace + (size_t)i * t.steps : nullptr;
+        int32_t *moved = t.move_log ? t.move_log + (size_t)i * t.steps * 2 : nullptr;
+        consider(0);
+        stop = stops();
+        std::vector<std::pair<int, int>> listed;                        // (estimate, position) of this move's candidates
+        for (int mv = 1; mv <= t.steps && stop == 0; ++mv) {
+            for (int at = 0; at < total; ++at) pos[seq[at]] = at;
+            for (int x = total - 1; x >= 0; --x) {                      // every successor of an operation was placed behind it
+                const int e = placed[x], m = mach_of(e);
+                int tl = e % mmax + 1 < M ? dur_of(e + 1) + tail[e + 1] : 0;
+                if (pos[e] + 1 < first[m + 1]) tl = std::max(tl, dur_of(seq[pos[e] + 1]) + tail[seq[pos[e] + 1]]);
+                tail[e] = tl;
+            }
+            auto E = [&](int e) { return start[e] + dur_of(e); };
+            auto Q = [&](int e) { return dur_of(e) + tail[e]; };
+            auto job_head = [&](int e) { return e % mmax > 0 ? E(e - 1) : 0; };
+            auto job_tail = [&](int e) { return e % mmax + 1 < M ? Q(e + 1) : 0; };
+            listed.clear();
+            int take = -1, take_est = 0;
+            for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+                for (int at = first[m]; at + 1 < first[m + 1]; ++at) {
+                    const int u = seq[at], v = seq[at + 1];
+                    if (!(g[u] > g[v])) continue;
+                    const int hv = std::max(job_head(v), at > first[m] ? E(seq[at - 1]) : 0);
+                    const int hu = std::max(job_head(u), hv + dur_of(v));
+                    const int tu = dur_of(u) + std::max(job_tail(u), at + 2 < first[m + 1] ? Q(seq[at + 2]) : 0);
+                    const int tv = dur_of(v) + std::max(job_tail(v), tu);
+                    const int est = std::max(hv + tv, hu + tu);
+                    listed.emplace_back(est, at);
+                    const bool has_s = u % mmax + 1 < M, has_p = v % mmax > 0;
+                    const bool sure = !has_s || !has_p || (u + 1 != v - 1 && start[v - 1] < E(u + 1));
+                    if (sure && (take < 0 || est < take_est)) take = at, take_est = est;
+                }
+            candidates += (int)listed.size();
+            int mk = -1;
+            if (take >= 0) {
+                std::swap(seq[take], seq[take + 1]);
+                mk = forward();
+                if (mk < 0) std::swap(seq[take], seq[take + 1]);        // (unreachable: the screen)
+            } else {
+                ++fallbacks;
+                std::sort(listed.begin(), listed.end());
+                for (const auto &c : listed) {
+                    take = c.second;
+                    std::swap(seq[take], seq[take + 1]);
+                    mk = forward();
+                    if (mk >= 0) break;
+                    std::swap(seq[take], seq[take + 1]);
+                    ++retries;
+                }
+            }
+            if (mk < 0) {                                               // (unreachable: jss_relink.h says why)
+                forward();                                              // the starts of the order left behind
+                stop = 4;
+                break;
+            }
+            cur = mk, moves = mv, dist -= 1;                            // (seq[take] is v now, seq[take + 1] is u)
+            if (trace) trace[mv - 1] = cur;
+            if (moved) moved[2 * (mv - 1)] = seq[take + 1], moved[2 * (mv - 1) + 1] = seq[take];
+            consider(mv);
+            stop = stops();
+        }
+        if (best_move < 0) {
+            best = cur;
+            write_positions(t.best_rank + (size_t)i * region);
+        }
+        t.best_makespan[i] = best;
+        if (t.last_makespan) t.last_makespan[i] = cur;
+        if (t.last_rank) write_positions(t.last_rank + (size_t)i * region);
+        if (trace)
+            for (int x = moves; x < t.steps; ++x) trace[x] = -1;
+        if (moved)
+            for (int x = 2 * moves; x < 2 * t.steps; ++x) moved[x] = -1;
+        if (t.info) {
+            int32_t *row = t.info + (size_t)i * JSS_RELINK_NI;
+            row[0] = stop, row[1] = moves, row[2] = best_move, row[3] = dist0;
+            row[4] = dist, row[5] = candidates, row[6] = fallbacks, row[7] = retries;
+        }
+    };
+    parallel_for<true>(d.batch, d.threads, one);
+    return 0;
+}
+
 }  // extern "C"

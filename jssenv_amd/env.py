@@ -1018,6 +1018,94 @@ class BatchedJssEnv:
             out += (ml,)
         return out
 
+    # -- path relinking between machine orders (jss_relink_walk, include/jss_relink.h) ------------------------------------------
+    def relink(self, rank, guide, steps=None, until=0, margin: int = 0, trace: bool = False, last: bool = True, log: bool = False):
+        """One walk per env from the machine order ``rank`` towards the machine order ``guide``, the whole walk in one launch
+        (include/jss_relink.h defines it; integers, the same bits on every backend).  ``rank`` (B, jmax, mmax) as in
+        ``evaluate_order`` (None: the env's own ``solution``), ``guide`` likewise.  A move swaps two operations adjacent on a
+        machine that the guide has the other way round, so it lowers the distance -- the number of pairs of operations of one
+        machine that the two orders put the other way round -- by one, and every order on the way has a schedule; the swap taken
+        is the one with the lowest head and tail estimate among those that surely close no cycle, and only it is re-timed.  The
+        walk ends on arrival, once the distance is <= ``until`` (an int or a (B,) array), or after ``steps`` moves (None:
+        65 536).  ``margin``: orders nearer than that to either end do not count as the best.  Only the instance tables are read.
+
+        Returns ``(best_makespan, best_rank, last_makespan, last_rank, info[, trace][, move_log])`` (``last=False`` leaves the
+        two ``last`` entries None): the lowest makespan on the path (-1 refused, -2 an order without a schedule) and its order as
+        positions, the same of the order the walk ended on, ``info`` (B, 8): stop (0 ``steps`` moves made, 1 arrived, 2 ``until``
+        reached, 4 never, -1 / -2), moves, the move that gave the best (-1: no order was eligible, the last one is returned), the
+        distance at the start, the distance at the end, candidates listed, moves without a sure candidate, candidates swapped
+        back; ``trace`` (B, steps) the makespan after every move and ``move_log`` (B, steps, 2) the flat indices of the two
+        operations swapped, -1 behind the last move.  Arrays of the env's backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before relink()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError("relink does not run while a step session is open on this env: close() it first")
+        from .search import relink_library
+        be = self.backend
+        lib = relink_library(be)
+        B, margin = self.batch, int(margin)
+        steps = _abi.RELINK_MAX_STEPS if steps is None else int(steps)
+        if not 0 <= steps <= _abi.RELINK_MAX_STEPS:
+            raise ValueError(f"relink: steps must be in [0, {_abi.RELINK_MAX_STEPS}]")
+        if margin < 0:
+            raise ValueError("relink: margin must be >= 0")
+        if guide is None:
+            raise ValueError("relink: a guide is needed")
+        with be.on_device():
+            rk = self.solution if rank is None else be.as_device(rank, "int32")
+            gd = be.as_device(guide, "int32")
+            for x, name in ((rk, "rank"), (gd, "guide")):
+                if tuple(x.shape) != (B, self.jmax, self.mmax):
+                    raise ValueError(f"relink: {name} must have shape {(B, self.jmax, self.mmax)}, got {tuple(x.shape)}")
+            until_of = None
+            if (until.ndim if hasattr(until, "ndim") else np.ndim(until)) == 0:
+                if int(until) < 0:
+                    raise ValueError("relink: until must be >= 0")
+            else:
+                until_of = be.as_device(until, "int32")
+                if getattr(be, "torch", None) is None:
+                    until_of = until_of.copy()                         # (as_device keeps ONE array alive)
+                if tuple(until_of.shape) != (B,):
+                    raise ValueError(f"relink: until must be an int or have shape {(B,)}")
+
+            def minus_one(shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            mk, best = minus_one((B,)), minus_one((B, self.jmax, self.mmax))
+            info = be.zeros((B, _abi.RELINK_NI), "int32")
+            lm = minus_one((B,)) if last else None
+            lr = minus_one((B, self.jmax, self.mmax)) if last else None
+            tr = minus_one((B, steps)) if trace else None
+            ml = minus_one((B, steps, 2)) if log else None
+            if B:
+                p = be.ptr
+                arg = _abi.JssRelink(steps, 0 if until_of is not None else int(until), margin, p(rk), p(gd), p(until_of), p(mk),
+                                     p(best), p(lm), p(lr), p(info), p(tr), p(ml))
+                rc = lib.jss_relink_walk(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_relink_walk")
+            self._relink_keep = [rk, gd, until_of]             # alive until the launch has read them
+        out = (mk, best, lm, lr, info)
+        if trace:
+            out += (tr,)
+        if log:
+            out += (ml,)
+        return out
+
+    def order_distance(self, rank, guide):
+        """(B,) int32: per env the number of pairs of operations of one machine that the machine orders ``rank`` and ``guide``
+        (as in ``relink``) put the other way round; -1 where either is refused, -2 where either has no schedule.  It is
+        ``relink`` with ``steps=0``."""
+        out = self.relink(rank, guide, steps=0, last=False)
+        mk, info = out[0], out[4]
+        be = self.backend
+        with be.on_device():
+            if getattr(be, "torch", None) is not None:
+                return be.torch.where(mk < 0, mk, info[:, 3])
+            return np.where(mk < 0, mk, info[:, 3]).astype(np.int32)
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

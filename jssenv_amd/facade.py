@@ -367,6 +367,31 @@ class JssEnv(gymnasium_base("Env")):
         host = [np.asarray(b.backend.numpy(x))[0] for x in out]
         return (int(host[0]),) + tuple(host[1:])
 
+    def _order_row(self, rank):
+        b = self._b
+        r = np.full((1, b.jmax, b.mmax), -1, np.int32)
+        rank = np.asarray(rank)
+        r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
+        return r
+
+    def relink(self, rank, guide, steps=None, until: int = 0, margin: int = 0, trace: bool = False, last: bool = True,
+               log: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.relink`` (include/jss_relink.h): one walk from the machine order ``rank`` (J x M or
+        jmax x mmax; None: this env's finished ``solution``) towards the machine order ``guide``.  Returns ``(best_makespan,
+        best_rank, last_makespan, last_rank, info[, trace][, move_log])``: ints (-1 refused, -2 no schedule) and host arrays."""
+        b = self._b
+        out = b.relink(None if rank is None else self._order_row(rank), self._order_row(guide), steps, int(until), margin, trace,
+                       last, log)
+        host = [None if x is None else np.asarray(b.backend.numpy(x))[0] for x in out]
+        return tuple(int(x) if k in (0, 2) and x is not None else x for k, x in enumerate(host))
+
+    def order_distance(self, rank, guide) -> int:
+        """The B = 1 form of ``BatchedJssEnv.order_distance``: the distance between two machine orders (-1 refused, -2 no
+        schedule)."""
+        b = self._b
+        out = b.order_distance(None if rank is None else self._order_row(rank), self._order_row(guide))
+        return int(np.asarray(b.backend.numpy(out))[0])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

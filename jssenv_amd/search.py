@@ -20,6 +20,11 @@ And tabu search over that neighbourhood (include/jss_tabu.h): ``tabu_reference``
 
 And the same walk over block insertions (include/jss_block.h): ``block_reference``, the NumPy mirror of ``jss_block_search``,
 ``block_library``, and ``tabu_search(moves="block")`` through ``BatchedJssEnv.tabu_blocks``.
+
+And path relinking between machine orders (include/jss_relink.h): ``relink_reference``, the NumPy mirror of ``jss_relink_walk``,
+``relink_library``, and ``relink_search``, the population driver: block walks whose walkers restart from a point on the path to
+their group's elite order, defined by ``tabu_blocks``, ``order_distance`` and ``relink`` (tests/relink_cases.py writes that loop
+out).
 """
 from __future__ import annotations
 
@@ -847,6 +852,150 @@ def block_reference(env_const, ops, rank, iters, tenure, target=None, reach=0, f
     return best_mk, best_rank, last_rank, info, trace, move_log
 
 
+# ---- path relinking between machine orders (include/jss_relink.h) ----------------------------------------------------------------
+def relink_library(backend):
+    """The library of ``backend`` that exports include/jss_relink.h: ``backend.relink_lib`` (HipBackend: libjss_relink_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
+    lib = getattr(backend, "relink_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.RELINK_SYMBOLS):
+            raise RuntimeError("relink: the backend's library does not export include/jss_relink.h")
+        _abi.bind_relink(lib)
+    return lib
+
+
+def relink_reference(env_const, ops, rank, guide, steps, until, margin=0, fill=-1, log=None):
+    """include/jss_relink.h's jss_relink_walk on host arrays, written from the header's definition on top of
+    ``order_eval_reference``, one walker after the other: the refusal and the cycle check of both rows, every move's starts and
+    tails and every re-timing are calls of that mirror; the orders, the distance, candidates, screen, estimate, choice and
+    fallback are written out here.  ``rank``, ``guide`` (B, jmax, mmax); ``until`` an int or (B,); ``margin`` an int.  Returns
+    ``(best_makespan, best_rank, last_makespan, last_rank, info, trace, move_log)``: int32 (B,), (B, jmax, mmax), (B,),
+    (B, jmax, mmax), (B, 8), (B, steps), (B, steps, 2).  The rows of refused (-1) and cyclic (-2) walkers hold ``fill`` in both
+    ranks, the trace and the move log.  ``log``: a list that receives ``(walker, move, event)``: "unsure" for a candidate the
+    screen did not pass, "fallback" for a move without a sure candidate, "retry" for a candidate the fallback swapped back."""
+    rank = np.asarray(rank, dtype=np.int64)
+    guide = np.asarray(guide, dtype=np.int64)
+    B, jmax, mmax = rank.shape
+    region, steps, margin = jmax * mmax, int(steps), int(margin)
+    const = np.asarray(env_const, dtype=np.int64).reshape(B, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    until = np.broadcast_to(np.asarray(until, dtype=np.int64), (B,))
+    best_mk = np.full(B, -1, np.int32)
+    last_mk = np.full(B, -1, np.int32)
+    best_rank = np.full((B, jmax, mmax), fill, np.int32)
+    last_rank = np.full((B, jmax, mmax), fill, np.int32)
+    info = np.zeros((B, _abi.RELINK_NI), np.int32)
+    trace = np.full((B, steps), fill, np.int32)
+    move_log = np.full((B, steps, 2), fill, np.int32)
+    note = (lambda *event: log.append(event)) if log is not None else (lambda *event: None)
+    of_source = order_eval_reference(const, ops, rank)[0]
+    of_guide = order_eval_reference(const, ops, guide)[0]
+    for i in range(B):
+        if of_source[i] == -1 or of_guide[i] == -1 or until[i] < 0:
+            best_mk[i] = last_mk[i] = info[i, 0] = -1
+            continue
+        if of_source[i] == -2 or of_guide[i] == -2:
+            best_mk[i] = last_mk[i] = info[i, 0] = -2
+            continue
+        J, M, tab = (int(x) for x in const[i, [_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE]])
+        one = const[i:i + 1]
+        mach = (ops[tab].reshape(-1) >> 16) & 63
+        dur = ops[tab].reshape(-1) & 0xFFFF
+        real = np.zeros((jmax, mmax), bool)
+        real[:J, :M] = True
+        real_ops = np.flatnonzero(real.reshape(-1))
+        machines = [real_ops[mach[real_ops] == m] for m in range(_abi.MAX_MACHINES)]
+
+        def positions(row):                                           # a rank row as positions on the machines
+            out = np.full(region, -1, np.int64)
+            for on in machines:
+                out[on[np.lexsort((on, row[on]))]] = np.arange(on.size)
+            return out
+
+        pos, g = positions(rank[i].reshape(-1)), positions(guide[i].reshape(-1))
+        dist = 0
+        for on in machines:
+            for a in on:
+                dist += int(((pos[on] > pos[a]) & (g[on] < g[a])).sum())
+        dist0 = dist
+        cur = int(of_source[i])
+        moves = candidates = fallbacks = retries = 0
+        best, best_move, best_pos = None, -1, None
+        if 0 >= margin and dist >= margin:
+            best, best_move, best_pos = cur, 0, pos.copy()
+        stops = lambda: 1 if dist == 0 else 2 if dist <= until[i] else 0   # noqa: E731
+        stop = stops()
+        for t in range(1, steps + 1):
+            if stop:
+                break
+            _, st, tl = order_eval_reference(one, ops, pos.reshape(1, jmax, mmax))[:3]
+            st, tl = st[0].reshape(-1).astype(np.int64), tl[0].reshape(-1).astype(np.int64)
+            E = lambda e: int(st[e] + dur[e]) if e >= 0 else 0       # noqa: E731  (a missing neighbour contributes 0)
+            Q = lambda e: int(dur[e] + tl[e]) if e >= 0 else 0       # noqa: E731
+            JP = lambda e: e - 1 if e % mmax > 0 else -1             # noqa: E731
+            JS = lambda e: e + 1 if e % mmax + 1 < M else -1         # noqa: E731
+            listed = []                                               # (estimate, listing index, u, v, sure)
+            for on in machines:
+                on = [int(e) for e in on[np.argsort(pos[on])]]
+                at_m = lambda a: on[a] if 0 <= a < len(on) else -1   # noqa: E731
+                for at in range(len(on) - 1):
+                    u, v = on[at], on[at + 1]
+                    if not g[u] > g[v]:
+                        continue
+                    s, p = JS(u), JP(v)
+                    sure = s < 0 or p < 0 or (s != p and st[p] < st[s] + dur[s])
+                    hv = max(E(p), E(at_m(at - 1)))
+                    hu = max(E(JP(u)), hv + int(dur[v]))
+                    tu = int(dur[u]) + max(Q(s), Q(at_m(at + 2)))
+                    tv = int(dur[v]) + max(Q(JS(v)), tu)
+                    if not sure:
+                        note(i, t, "unsure")
+                    listed.append((max(hv + tv, hu + tu), len(listed), u, v, sure))
+            candidates += len(listed)
+
+            def swapped(u, v):
+                out = pos.copy()
+                out[u], out[v] = pos[v], pos[u]
+                return out, int(order_eval_reference(one, ops, out.reshape(1, jmax, mmax))[0][0])
+
+            taken = None
+            sure = [c for c in listed if c[4]]
+            if sure:
+                _, _, u, v, _ = min(sure)
+                new, mk = swapped(u, v)
+                if mk >= 0:
+                    taken = (u, v, new, mk)
+            else:
+                fallbacks += 1
+                note(i, t, "fallback")
+                for _, _, u, v, _ in sorted(listed):
+                    new, mk = swapped(u, v)
+                    if mk >= 0:
+                        taken = (u, v, new, mk)
+                        break
+                    retries += 1
+                    note(i, t, "retry")
+            if taken is None:                                         # (the header says why this is unreachable)
+                stop = 4
+                break
+            u, v, pos, cur = taken
+            moves, dist = t, dist - 1
+            trace[i, t - 1] = cur
+            move_log[i, t - 1] = (u, v)
+            if t >= margin and dist >= margin and (best is None or cur < best):
+                best, best_move, best_pos = cur, t, pos.copy()
+            stop = stops()
+        if best is None:
+            best, best_pos = cur, pos
+        best_mk[i], last_mk[i] = best, cur
+        best_rank[i], last_rank[i] = best_pos.reshape(jmax, mmax), pos.reshape(jmax, mmax)
+        trace[i, moves:] = -1
+        move_log[i, moves:] = -1
+        info[i] = (stop, moves, best_move, dist0, dist, candidates, fallbacks, retries)
+    return best_mk, best_rank, last_mk, last_rank, info, trace, move_log
+
+
 @dataclass
 class TabuResult:
     """What ``tabu_search`` returns, host arrays.  Per instance: ``makespan`` (G,), the lowest ``(best_makespan, walker)`` of its
@@ -936,3 +1085,116 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
         proven |= (mk >= 0) & (mk <= tgt)
     return TabuResult(makespan=mk[winner], walker=walker, rank=host(best_rank)[winner].copy(), start=host(start).copy(),
                       optimal=proven[winner], best_makespan=mk, info=info, target=tgt, tenure=ten, env=env)
+
+
+@dataclass
+class RelinkResult(TabuResult):
+    """What ``relink_search`` returns: ``TabuResult``'s fields -- ``best_makespan`` (S,) the walkers' bests over all stages,
+    ``info`` (S, 8) that of the block walk that gave a walker its best -- and ``history`` (G, rounds + 1), the group's best
+    after the first walk and after every round, and ``distance`` (S, rounds), every walker's distance to its group's elite
+    order at the start of every round."""
+    history: Optional[np.ndarray] = None
+    distance: Optional[np.ndarray] = None
+
+
+def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share=(1, 2), tenure=(5, 12), explore=0.1, seed=0,
+                  target="lower_bound", reach=0, device=None, _backend=None):
+    """Block-insertion tabu walks whose walkers learn from their group's best one (after Nowicki and Smutnicki's i-TSAB): one group
+    of ``walkers`` envs per instance, all in one batch, as ``tabu_search`` lays them out.  Defined by public calls alone:
+
+    start   exactly ``tabu_search(moves="block")``'s: the batch, ``reset``, the target, ``rollout(kind, explore, seed)``, the
+            tenures, and one ``tabu_blocks(None, iters, tenures, target, reach)``: ``best`` and ``best_rank`` per walker.
+    round   (``rounds`` of them) the elite of a group is its walker with the lowest ``(best, walker)``; every walker's guide is
+            its group's elite order, gathered on the device; ``d = order_distance(best_rank, guide)``;
+            ``relink(best_rank, guide, until=d - d * share[0] // share[1])`` walks that share of the way towards the elite (a
+            walker that is already at its target gets ``until = d`` and stays put; the elite has distance 0 and simply walks on
+            from its best order); ``tabu_blocks(last_rank, iters, tenures, target, reach)`` walks on from where the relinking
+            ended; a walker keeps the lower of its old and its new best, the old one on a tie, with its order and that walk's
+            ``info`` (a ``where`` on the device).  Nothing comes back to the host inside a round.
+    end     as ``tabu_search``: the lowest ``(best, walker)`` of every group, one ``evaluate_order`` for its start times.
+
+    ``rounds=0`` returns what ``tabu_search(moves="block")`` returns, in the fields they share.  Returns a ``RelinkResult``."""
+    W, rounds, reach = int(walkers), int(rounds), int(reach)
+    if W < 1:
+        raise ValueError("relink_search: walkers must be >= 1")
+    if rounds < 0:
+        raise ValueError("relink_search: rounds must be >= 0")
+    num, den = (int(x) for x in share)
+    if not (den >= 1 and 0 <= num <= den):
+        raise ValueError("relink_search: share is (a, b) with 0 <= a <= b and b >= 1")
+    if not 0 <= reach <= _abi.BLOCK_MAX_REACH:
+        raise ValueError(f"relink_search: reach must lie in [0, {_abi.BLOCK_MAX_REACH}]")
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError("relink_search takes instances (a name, a path, an Instance, or a list of them): call relink and "
+                                  "tabu_blocks on a BatchedJssEnv for anything else")
+    one = isinstance(instances, (str, os.PathLike, Instance))
+    names = [instances] if one else list(instances)
+    G = len(names)
+    if G < 1:
+        raise ValueError("relink_search: need at least one instance")
+    lo, hi = (int(tenure), int(tenure)) if np.ndim(tenure) == 0 else (int(tenure[0]), int(tenure[1]))
+    if not 0 <= lo <= hi <= _abi.TABU_MAX_TENURE:
+        raise ValueError(f"relink_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}], low <= high")
+    S = G * W
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+    if G == 1:
+        env = BatchedJssEnv(names[0], batch=S, seed=int(seed or 0), **kw)
+    else:
+        env = BatchedJssEnv(names, batch=S, table_of_env=np.repeat(np.arange(G), W), order="interleaved", seed=int(seed or 0), **kw)
+    be = env.backend
+    env.reset()
+    if isinstance(target, str):
+        if target != "lower_bound":
+            raise ValueError("relink_search: target is 'lower_bound', None, an int or one int per instance")
+        tgt = env.lower_bound()
+    elif target is None:
+        tgt = None
+    else:
+        tgt = np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), W)
+    env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False, explore=explore, seed=seed)
+    ten = (lo + (np.arange(S) % W) % (hi - lo + 1)).astype(np.int32)
+    best, best_rank, info = env.tabu_blocks(None, iters, ten, tgt, reach)
+    xp = be.torch if getattr(be, "torch", None) is not None else np
+    with be.on_device():
+        on = lambda x, dtype: be.from_numpy(np.asarray(x, dtype))   # noqa: E731
+        first = on(np.arange(G) * W, np.int64)                       # the groups' first walkers
+        group = on(np.repeat(np.arange(G), W), np.int64)             # every walker's group
+        ten_dev = on(ten, np.int32)
+        tgt_dev = None if tgt is None else on(tgt, np.int32) if isinstance(tgt, np.ndarray) else tgt
+        never = 2 ** 31 - 1
+
+        def group_low(mk):                                           # (G, W): a walker without a schedule counts as +inf
+            return xp.where(mk >= 0, mk, never).reshape(G, W)
+
+        history, distance = [group_low(best).min(1) if xp is np else group_low(best).min(1).values], []
+        for _ in range(rounds):
+            elite = first + group_low(best).argmin(1)                # (the first of equal makespans)
+            guide = best_rank[elite[group]]
+            d = env.order_distance(best_rank, guide)
+            until = d - d * num // den
+            if tgt_dev is not None:
+                until = xp.where((best >= 0) & (best <= tgt_dev), d, until)
+            last_rank = env.relink(best_rank, guide, None, until)[3]
+            new, new_rank, new_info = env.tabu_blocks(last_rank, iters, ten_dev, tgt_dev, reach)
+            keep = (new >= 0) & ((best < 0) | (new < best))
+            best = xp.where(keep, new, best)
+            best_rank = xp.where(keep[:, None, None], new_rank, best_rank)
+            info = xp.where(keep[:, None], new_info, info)
+            history.append(group_low(best).min(1) if xp is np else group_low(best).min(1).values)
+            distance.append(d)
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    mk, info = host(best).astype(np.int32), host(info).astype(np.int32)
+    tgt = None if tgt is None else host(tgt).astype(np.int32)
+    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
+    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
+    winner = (np.arange(G) * W + walker).astype(np.int32)
+    again, start = env.evaluate_order(best_rank, winner, start=True)
+    assert np.array_equal(host(again), mk[winner])
+    proven = info[:, 0] == 1
+    if tgt is not None:
+        proven |= (mk >= 0) & (mk <= tgt)
+    return RelinkResult(makespan=mk[winner], walker=walker, rank=host(best_rank)[winner].copy(), start=host(start).copy(),
+                        optimal=proven[winner], best_makespan=mk, info=info, target=tgt, tenure=ten, env=env,
+                        history=np.stack([host(h) for h in history], axis=1).astype(np.int32),
+                        distance=np.stack([host(x) for x in distance], axis=1).astype(np.int32).reshape(S, rounds) if rounds
+                        else np.zeros((S, 0), np.int32))

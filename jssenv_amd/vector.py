@@ -112,6 +112,14 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
                                   "(search.tabu_search takes a list of instances)")
 
+    def relink(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not relink machine orders: call relink on a BatchedJssEnv "
+                                  "(search.relink_search takes a list of instances)")
+
+    def order_distance(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
+                                  "(search.relink_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
