@@ -127,6 +127,14 @@ RELINK_SYMBOLS = ("jss_relink_walk",)
 RELINK_NI = 8                     # info row: stop, moves, best_move, dist0, dist, candidates, fallbacks, retries
 RELINK_MAX_STEPS = 65536
 
+# include/jss_decode.h: the companion header of Giffler-Thompson decoding of key tables and of one BRKGA generation (its own
+# version).  The HIP library exports both from an eighth library, libjss_decode_hip.so; the twin from libjss_cpu.so.
+DECODE_VERSION = 1
+DECODE_SYMBOLS = ("jss_decode_keys", "jss_keys_evolve")
+DECODE_NI = 4                     # info row: conflicts, widest, delayed, 0
+EVOLVE_SEED_XOR = 0xD1B54A32D192ED03   # keys jss_keys_evolve's counter RNG: rng_u32(seed ^ EVOLVE_SEED_XOR, row, generation, x)
+EVOLVE_MAX_POP = 4096
+
 _p = C.c_void_p
 
 
@@ -219,6 +227,17 @@ class JssRelink(C.Structure):        # include/jss_relink.h
     _fields_ = [("steps", C.c_int32), ("until", C.c_int32), ("margin", C.c_int32), ("rank", _p), ("guide", _p), ("until_of", _p),
                 ("best_makespan", _p), ("best_rank", _p), ("last_makespan", _p), ("last_rank", _p), ("info", _p), ("trace", _p),
                 ("move_log", _p)]
+
+
+class JssDecode(C.Structure):        # include/jss_decode.h
+    _fields_ = [("n", C.c_int32), ("stride", C.c_int32), ("delta_q16", C.c_int32), ("parents", _p), ("keys", _p), ("delta_of", _p),
+                ("makespan", _p), ("start", _p), ("info", _p)]
+
+
+class JssEvolve(C.Structure):        # include/jss_decode.h
+    _fields_ = [("groups", C.c_int32), ("pop", C.c_int32), ("region", C.c_int32), ("n_elite", C.c_int32), ("n_mutant", C.c_int32),
+                ("rho_q16", C.c_int32), ("generation", C.c_int32), ("seed", C.c_uint64), ("fitness", _p), ("keys_in", _p),
+                ("keys_out", _p), ("by_rank", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -379,6 +398,18 @@ def bind_relink(lib):
             raise AttributeError(f"library does not export {name}")
     lib.jss_relink_walk.restype = C.c_int
     lib.jss_relink_walk.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssRelink), _p]
+    return lib
+
+
+def bind_decode(lib):
+    """Attach the prototypes of include/jss_decode.h; raises AttributeError naming the first missing symbol."""
+    for name in DECODE_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_decode_keys.restype = C.c_int
+    lib.jss_decode_keys.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssDecode), _p]
+    lib.jss_keys_evolve.restype = C.c_int
+    lib.jss_keys_evolve.argtypes = [C.POINTER(JssEvolve), _p]
     return lib
 
 

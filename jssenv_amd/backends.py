@@ -51,6 +51,7 @@ class HipBackend:
         self._tabu_lib = None
         self._block_lib = None
         self._relink_lib = None
+        self._decode_lib = None
 
     @property
     def beam_lib(self):
@@ -111,6 +112,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_relink_extension)")
             self._relink_lib = _abi.bind_relink(C.CDLL(path))
         return self._relink_lib
+
+    @property
+    def decode_lib(self):
+        """libjss_decode_hip.so (include/jss_decode.h), loaded on first use; a missing library is an error."""
+        if self._decode_lib is None:
+            path = _abi.library_path("libjss_decode_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_decode_extension)")
+            self._decode_lib = _abi.bind_decode(C.CDLL(path))
+        return self._decode_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -329,6 +340,11 @@ class CpuBackend:
     def relink_lib(self):
         """the library that exports include/jss_relink.h: the twin itself"""
         return _abi.bind_relink(self.lib)
+
+    @property
+    def decode_lib(self):
+        """the library that exports include/jss_decode.h: the twin itself"""
+        return _abi.bind_decode(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -230,6 +230,14 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
                                   "(search.relink_search takes a list of instances)")
 
+    def decode_keys(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not decode key tables: call decode_keys on a BatchedJssEnv "
+                                  "(search.brkga_search takes a list of instances)")
+
+    def evolve_keys(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
+                                  "(search.brkga_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

@@ -7,6 +7,8 @@
 * ``libjss_tabu_hip.so`` -- the tabu-search kernel (include/jss_tabu.h), a fifth HIP library built the same way;
 * ``libjss_block_hip.so`` -- the block-insertion tabu kernel (include/jss_block.h), a sixth HIP library built the same way;
 * ``libjss_relink_hip.so`` -- the path-relinking kernel (include/jss_relink.h), a seventh HIP library built the same way;
+* ``libjss_decode_hip.so`` -- the Giffler-Thompson decoder of key tables and the BRKGA generation kernels (include/jss_decode.h),
+  an eighth HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -46,8 +48,12 @@ BLOCK_OUT = os.path.join(_HERE, "libjss_block_hip.so")
 _RELINK = os.path.join(_ROOT, "include", "jss_relink.h")     # ... and path relinking between machine orders (jss_relink_walk)
 RELINK_SRC = os.path.join(_HERE, "csrc", "jss_relink.hip")   # (libjss_relink_hip.so: a library of its own as well)
 RELINK_OUT = os.path.join(_HERE, "libjss_relink_hip.so")
+_DECODE = os.path.join(_ROOT, "include", "jss_decode.h")     # ... and Giffler-Thompson decoding of key tables, one BRKGA generation
+DECODE_SRC = os.path.join(_HERE, "csrc", "jss_decode.hip")   # (libjss_decode_hip.so: a library of its own as well)
+DECODE_OUT = os.path.join(_HERE, "libjss_decode_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
-                os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC))   # sources that libjss_hip.so does not include
+                os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC),
+                os.path.basename(DECODE_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -65,7 +71,7 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
@@ -73,6 +79,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
         build_tabu_extension(force)
         build_block_extension(force)
         build_relink_extension(force)
+        build_decode_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -80,7 +87,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -89,7 +96,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -98,7 +105,7 @@ def build_bound_extension(force: bool = False) -> str:
 
 
 def build_order_extension(force: bool = False) -> str:
-    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return ORDER_OUT
     tmp = ORDER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
@@ -107,7 +114,7 @@ def build_order_extension(force: bool = False) -> str:
 
 
 def build_tabu_extension(force: bool = False) -> str:
-    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return TABU_OUT
     tmp = TABU_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, TABU_SRC, "-o", tmp])
@@ -116,7 +123,7 @@ def build_tabu_extension(force: bool = False) -> str:
 
 
 def build_block_extension(force: bool = False) -> str:
-    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return BLOCK_OUT
     tmp = BLOCK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BLOCK_SRC, "-o", tmp])
@@ -125,7 +132,7 @@ def build_block_extension(force: bool = False) -> str:
 
 
 def build_relink_extension(force: bool = False) -> str:
-    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return RELINK_OUT
     tmp = RELINK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, RELINK_SRC, "-o", tmp])
@@ -133,8 +140,17 @@ def build_relink_extension(force: bool = False) -> str:
     return RELINK_OUT
 
 
+def build_decode_extension(force: bool = False) -> str:
+    if not force and _fresh(DECODE_OUT, [DECODE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
+        return DECODE_OUT
+    tmp = DECODE_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, DECODE_SRC, "-o", tmp])
+    os.replace(tmp, DECODE_OUT)
+    return DECODE_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -19,6 +19,7 @@
 #include "jss_tabu.h"
 #include "jss_block.h"
 #include "jss_relink.h"
+#include "jss_decode.h"
 
 namespace jss_abi {
 
@@ -429,6 +430,36 @@ inline int relink_check(const JssDesc *d, const JssState *s, const JssRelink *r)
     if (r->steps < 0 || r->steps > 65536) return JSS_E_SHAPE;
     if (r->until < 0 || r->margin < 0) return JSS_E_SHAPE;
     return relink_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// ---- Giffler-Thompson decoding of key tables, one BRKGA generation (include/jss_decode.h) ------------------------------------
+// What libjss_decode_hip.so keeps in LDS for one candidate, for the whole decode: the op row and the key row (int32) over the
+// entries of a [jmax][mmax] row rounded up to a multiple of 8, and one word per machine.
+inline long long decode_lds_bytes(int jmax, int mmax) { return 8 * order_entries8(jmax, mmax) + 64 * 4; }
+
+// jss_decode_keys (libjss_decode_hip.so and the twin): the batch as jss_order_eval checks it
+inline int decode_check(const JssDesc *d, const JssState *s, const JssDecode *k) {
+    if (!d || !s || !k) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!k->keys || !k->makespan) return JSS_E_NULL;
+    if (k->n < 0 || (!k->parents && k->n != d->batch)) return JSS_E_SHAPE;
+    if (k->stride != 0 && k->stride != d->jmax * d->mmax) return JSS_E_SHAPE;
+    if (k->delta_q16 < 0 || k->delta_q16 > 65536) return JSS_E_SHAPE;
+    return decode_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// jss_keys_evolve (libjss_decode_hip.so and the twin)
+inline int evolve_check(const JssEvolve *e) {
+    if (!e || !e->keys_out) return JSS_E_NULL;
+    if (e->pop < 1 || e->pop > JSS_EVOLVE_MAX_POP || e->region < 1 || e->groups < 0) return JSS_E_SHAPE;
+    if (e->n_elite < 0 || e->n_mutant < 0 || e->rho_q16 < 0 || e->rho_q16 > 65536) return JSS_E_SHAPE;
+    if ((long long)e->n_elite + e->n_mutant > e->pop) return JSS_E_SHAPE;
+    if (e->n_elite + e->n_mutant < e->pop && e->n_elite < 1) return JSS_E_SHAPE;
+    const bool all_mutants = e->n_elite == 0 && e->n_mutant == e->pop;
+    if (!all_mutants && (!e->fitness || !e->keys_in)) return JSS_E_NULL;
+    if (e->keys_out == e->keys_in) return JSS_E_NULL;
+    return 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -2068,4 +2068,98 @@ int jss_relink_walk(const JssDesc *desc, const JssState *state, const JssRelink 
     return 0;
 }
 
+// include/jss_decode.h: the definition, candidate by candidate, every iteration a scan over the jobs.
+int jss_decode_keys(const JssDesc *desc, const JssState *state, const JssDecode *decode, void *) {
+    if (const int rc = decode_check(desc, state, decode)) return rc;
+    const JssDesc d = *desc;
+    const JssDecode t = *decode;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int c) {
+        const int parent = t.parents ? t.parents[c] : c;
+        if (parent < 0 || parent >= d.batch) return void(t.makespan[c] = -1);
+        const int32_t *ec = state->env_const + (size_t)parent * JSS_NC;
+        const int J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return void(t.makespan[c] = -1);
+        const long long delta = t.delta_of ? t.delta_of[c] : t.delta_q16;
+        if (delta < 0 || delta > 65536) return void(t.makespan[c] = -1);
+        const int32_t *ops = d.ops + (size_t)tab * region, *keys = t.keys + (size_t)c * t.stride;
+        int32_t *start = t.start ? t.start + (size_t)c * region : nullptr;
+        if (start) std::fill(start, start + region, -1);
+        int k[JSS_MAX_JOBS], jobend[JSS_MAX_JOBS], est[JSS_MAX_JOBS], rel[JSS_MAX_MACHINES];
+        std::fill(k, k + J, 0), std::fill(jobend, jobend + J, 0), std::fill(rel, rel + JSS_MAX_MACHINES, 0);
+        auto mach_of = [&](int j) { return (ops[j * mmax + k[j]] >> 16) & 63; };
+        auto dur_of = [&](int j) { return ops[j * mmax + k[j]] & kDurMask; };
+        int conflicts = 0, widest = 0, delayed = 0;
+        for (int it = 0; it < J * M; ++it) {
+            int js = -1, cs = 0;
+            for (int j = 0; j < J; ++j) {
+                if (k[j] >= M) continue;
+                est[j] = std::max(jobend[j], rel[mach_of(j)]);
+                if (js < 0 || est[j] + dur_of(j) < cs) js = j, cs = est[j] + dur_of(j);
+            }
+            const int ms = mach_of(js);
+            int e0 = cs;
+            for (int j = 0; j < J; ++j)
+                if (k[j] < M && mach_of(j) == ms) e0 = std::min(e0, est[j]);
+            int pick = -1, size = 0;
+            for (int j = 0; j < J; ++j) {
+                if (k[j] >= M || mach_of(j) != ms) continue;
+                if (est[j] != e0 && !((long long)(est[j] - e0) * 65536 < delta * (cs - e0))) continue;
+                ++size;
+                if (pick < 0 || keys[j * mmax + k[j]] > keys[pick * mmax + k[pick]]) pick = j;
+            }
+            conflicts += size > 1, widest = std::max(widest, size), delayed += est[pick] > e0;
+            const int s = est[pick];
+            if (start) start[pick * mmax + k[pick]] = s;
+            jobend[pick] = rel[ms] = s + dur_of(pick);
+            k[pick] += 1;
+        }
+        t.makespan[c] = *std::max_element(jobend, jobend + J);
+        if (t.info) {
+            int32_t *row = t.info + (size_t)c * JSS_DECODE_NI;
+            row[0] = conflicts, row[1] = widest, row[2] = delayed, row[3] = 0;
+        }
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+// include/jss_decode.h: one BRKGA generation, group by group: the ranking by a sort, then the children row by row.
+int jss_keys_evolve(const JssEvolve *evolve, void *) {
+    if (const int rc = evolve_check(evolve)) return rc;
+    const JssEvolve t = *evolve;
+    const int P = t.pop, region = t.region;
+    const bool ranked = t.n_elite > 0 || t.n_mutant < P;              // (an initial population reads nothing)
+    auto one = [&](int g) {
+        std::vector<int> by_rank((size_t)P);
+        for (int p = 0; p < P; ++p) by_rank[p] = p;
+        if (ranked) {
+            const int32_t *fit = t.fitness + (size_t)g * P;
+            std::sort(by_rank.begin(), by_rank.end(), [&](int x, int y) {
+                if ((fit[x] < 0) != (fit[y] < 0)) return fit[y] < 0;
+                return fit[x] != fit[y] ? fit[x] < fit[y] : x < y;
+            });
+        }
+        if (t.by_rank) std::copy(by_rank.begin(), by_rank.end(), t.by_rank + (size_t)g * P);
+        for (int c = 0; c < P; ++c) {
+            const uint64_t i = (uint64_t)g * P + c;
+            int32_t *out = t.keys_out + (size_t)i * region;
+            auto R = [&](uint32_t x) { return rng_u32(t.seed ^ JSS_EVOLVE_SEED_XOR, i, (uint32_t)t.generation, x); };
+            if (c < t.n_elite) {
+                const int32_t *src = t.keys_in + ((size_t)g * P + by_rank[c]) * region;
+                std::copy(src, src + region, out);
+            } else if (c >= P - t.n_mutant) {
+                for (int e = 0; e < region; ++e) out[e] = (int32_t)R((uint32_t)e);
+            } else {
+                const int a = by_rank[R((uint32_t)region) % (uint32_t)t.n_elite];
+                const int b = by_rank[t.n_elite + R((uint32_t)region + 1u) % (uint32_t)(P - t.n_elite)];
+                const int32_t *pa = t.keys_in + ((size_t)g * P + a) * region, *pb = t.keys_in + ((size_t)g * P + b) * region;
+                for (int e = 0; e < region; ++e) out[e] = (int)(R((uint32_t)e) >> 16) < t.rho_q16 ? pa[e] : pb[e];
+            }
+        }
+    };
+    parallel_for<true>(t.groups, 0, one);
+    return 0;
+}
+
 }  // extern "C"

@@ -475,8 +475,23 @@ def keys_from_floats(x):
     return np.where(b >= 0, b, b ^ np.int32(0x7FFFFFFF)).astype(np.int32)
 
 
+def keys_from_schedule(start):
+    """Start times as a key table: ``-start`` as int32, 0 in the padding (the entries below 0) -- an array of any leading shape, a
+    NumPy array or a tensor.  The round trip: for every schedule ``S`` that a Giffler-Thompson decode with ``delta=1`` produced
+    (``BatchedJssEnv.decode_keys``, include/jss_decode.h), ``decode_keys(keys_from_schedule(S), delta=1)`` gives ``S`` back exactly.
+    Such an ``S`` is an active schedule, and among the unscheduled operations of a machine the one it starts first is always in
+    the conflict set, where its key, the largest, wins.  So a schedule a search has improved -- by ``tabu_blocks``, ``relink`` --
+    goes back into a population of key tables as long as it is active."""
+    if hasattr(start, "is_floating_point"):                              # a torch tensor
+        import torch
+        s = start.to(torch.int32)
+        return torch.where(s < 0, torch.zeros_like(s), -s)
+    s = np.asarray(start).astype(np.int32)
+    return np.where(s < 0, 0, -s).astype(np.int32)
+
+
 def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, explore: float = 0.0, seed: int = 0,
-                  return_solution: bool = False, _backend=None):
+                  return_solution: bool = False, _backend=None, decoder: str = "env", delta: float = 1.0):
     """Makespans of a population of key tables: ``keys`` is (P, J, M) int32 -- a NumPy array, or a tensor on the host or on the
     device --, one chromosome per row; one env per table is reset and decoded to the end by one ``jss_key_rollout``.  Returns
     the (P,) makespans, a NumPy int64 array; with ``return_solution`` also the (P, J, M) start times of the decoded schedules
@@ -484,8 +499,15 @@ def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, e
     for ``BatchedJssEnv`` ('cpu' = the host twin).
 
     Every call builds its batch anew, as ``evaluate_weights`` does: a loop over generations keeps one
-    ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and ``rollout("keys", keys=k, autoreset=False)`` on it."""
+    ``BatchedJssEnv(instance, batch=P)`` and calls ``reset()`` and ``rollout("keys", keys=k, autoreset=False)`` on it.
+
+    ``decoder="env"`` is that decode, through the env's own dynamics.  ``decoder="active"`` decodes by Giffler and Thompson's
+    procedure instead (``BatchedJssEnv.decode_keys``, include/jss_decode.h) with the delay parameter ``delta`` in [0, 1] -- 1:
+    active schedules, 0: non-delay schedules -- on ONE env that is only read; ``nope_key``, ``explore`` and ``seed`` play no part
+    in it."""
     from .env import BatchedJssEnv, play_to_end
+    if decoder not in ("env", "active"):
+        raise ValueError("evaluate_keys: decoder is 'env' or 'active'")
     inst = _instance_of(instance)
     J, M = inst.jobs, inst.machines
     k = keys if hasattr(keys, "is_floating_point") else np.ascontiguousarray(np.asarray(keys))
@@ -496,10 +518,15 @@ def evaluate_keys(instance, keys, nope_key: Optional[int] = None, device=None, e
         ms = np.zeros((0,), dtype=np.int64)
         return (ms, np.zeros((0, J, M), dtype=np.int64)) if return_solution else ms
     kw = {"_backend": _backend} if _backend is not None else {"device": device}
-    env = BatchedJssEnv(inst, batch=P, seed=int(seed), **kw)
+    env = BatchedJssEnv(inst, batch=1 if decoder == "active" else P, seed=int(seed), **kw)
     if hasattr(k, "is_floating_point") and getattr(env.backend, "torch", None) is None:
         k = k.detach().cpu().numpy()                                      # a tensor, and the host twin's NumPy memory
     env.reset()
+    if decoder == "active":
+        out = env.decode_keys(k, np.zeros(P, np.int32), delta, start=return_solution)
+        if return_solution:
+            return tuple(env.backend.numpy(x).astype(np.int64) for x in out)
+        return env.backend.numpy(out).astype(np.int64).reshape(P)
     play_to_end(env, "keys", explore, keys=k, nope_key=nope_key)
     ms = env.backend.numpy(env.makespan).astype(np.int64).reshape(P)
     if return_solution:

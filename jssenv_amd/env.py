@@ -1106,6 +1106,132 @@ class BatchedJssEnv:
                 return be.torch.where(mk < 0, mk, info[:, 3])
             return np.where(mk < 0, mk, info[:, 3]).astype(np.int32)
 
+    # -- Giffler-Thompson decoding of key tables, one BRKGA generation (include/jss_decode.h) ----------------------------------
+    def decode_keys(self, keys, parents=None, delta=1.0, start: bool = False, info: bool = False):
+        """Key tables decoded into schedules by Giffler and Thompson's procedure, one decode per candidate in one launch
+        (include/jss_decode.h defines it; integers, the same bits on every backend).  ``keys`` is int32 ``(jmax, mmax)`` -- one
+        table for every candidate -- or ``(n, jmax, mmax)``, table c for candidate c, on the host or on the device; candidate c
+        decodes on the instance of env ``parents[c]`` (``None``: env c, and n == B).  Among the operations in conflict on the
+        machine of the earliest possible completion, the one with the largest key goes first (the lowest job index on ties).
+        ``delta`` in [0, 1], a float or an ``(n,)`` array of floats, is the delay parameter: 1 gives active schedules (the class
+        that always holds an optimum), 0 non-delay schedules, in between Bierwirth and Mattfeld's hybrid; it is converted by
+        ``round(delta * 65536)``.  Only the instance tables are read: no env is stepped or written.
+
+        Returns ``makespan`` (n,) int32 (-1 refused: a parent out of range or never reset), then with ``start`` the
+        ``(n, jmax, mmax)`` start times (-1 in the padding: a rank tensor for ``evaluate_order``, ``tabu_blocks`` and ``relink``),
+        then with ``info`` the ``(n, 4)`` counters (iterations with more than one operation in conflict, the largest conflict
+        set, iterations whose chosen operation could not start earliest, 0).  Arrays of the env's backend."""
+        if not self._is_reset:
+            raise RuntimeError("call reset() before decode_keys()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError("decode_keys does not run while a step session is open on this env: close() it first")
+        from .search import decode_library
+        be = self.backend
+        lib = decode_library(be)
+        B, region = self.batch, self.jmax * self.mmax
+        with be.on_device():
+            k = be.as_device(keys, "int32")
+            shape = tuple(k.shape)
+            if not (shape == (self.jmax, self.mmax) or (len(shape) == 3 and shape[1:] == (self.jmax, self.mmax))):
+                raise ValueError(f"decode_keys: keys must have shape {(self.jmax, self.mmax)} or (n, {self.jmax}, {self.mmax}), got {shape}")
+            par = None
+            if parents is not None:
+                par = be.as_device(parents, "int32")
+                if getattr(be, "torch", None) is None:
+                    par = par.copy()                                   # (as_device keeps ONE array alive)
+                if len(par.shape) != 1:
+                    raise ValueError("decode_keys: parents must have shape (n,)")
+            n = int(par.shape[0]) if par is not None else shape[0] if len(shape) == 3 else B
+            if len(shape) == 3 and shape[0] != n:
+                raise ValueError(f"decode_keys: {shape[0]} key tables for {n} candidates")
+            if par is None and n != B:
+                raise ValueError(f"decode_keys: without parents there is one candidate per env ({B}), got {n}")
+            delta_of, delta_q16 = None, 0
+            if (delta.ndim if hasattr(delta, "ndim") else np.ndim(delta)) == 0:
+                if not 0.0 <= float(delta) <= 1.0:
+                    raise ValueError("decode_keys: delta must lie in [0, 1]")
+                delta_q16 = int(round(float(delta) * 65536))
+            else:
+                d = np.asarray(delta.detach().cpu() if hasattr(delta, "detach") else delta, np.float64)
+                if d.shape != (n,):
+                    raise ValueError(f"decode_keys: delta must be a float or have shape {(n,)}")
+                if not ((d >= 0.0) & (d <= 1.0)).all():
+                    raise ValueError("decode_keys: delta must lie in [0, 1]")
+                delta_of = be.from_numpy(np.round(d * 65536).astype(np.int32))
+            mk = be.zeros((n,), "int32")
+            mk -= 1
+            st = nf = None
+            if start:
+                st = be.zeros((n, self.jmax, self.mmax), "int32")
+                st -= 1
+            if info:
+                nf = be.zeros((n, _abi.DECODE_NI), "int32")
+            if n:
+                p = be.ptr
+                arg = _abi.JssDecode(n, region if len(shape) == 3 else 0, delta_q16, p(par), p(k), p(delta_of), p(mk), p(st), p(nf))
+                rc = lib.jss_decode_keys(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_decode_keys")
+            self._decode_keep = [k, par, delta_of]             # alive until the launch has read them
+        out = (mk,)
+        if start:
+            out += (st,)
+        if info:
+            out += (nf,)
+        return out[0] if len(out) == 1 else out
+
+    def evolve_keys(self, keys, fitness, pop: int, elite: int, mutants: int, rho: float = 0.7, generation: int = 1, seed=None):
+        """One generation of a biased random-key genetic algorithm over key tables, on the device (``jss_keys_evolve``,
+        include/jss_decode.h; integers, the same bits on every backend).  ``keys`` is int32 ``(G * pop, ...)``: G groups of
+        ``pop`` individuals, every row one individual (its trailing axes are flattened); ``fitness`` int32 ``(G * pop,)``, lower
+        is better, a negative value (a refused decode) behind every other.  Of every group the ``elite`` best are copied, the
+        last ``mutants`` rows are drawn anew, and every row between is a crossover of a random elite and a random non-elite
+        individual, each entry from the elite parent with probability ``rho``.  ``elite=0, mutants=pop`` draws an initial
+        population: ``keys`` is then the shape ``(G * pop, ...)`` (or an array of that shape) and ``fitness`` may be None.
+        ``seed`` None: the env's own.  Returns ``(keys_out, by_rank)``: the new rows in the shape of ``keys`` and ``(G * pop,)``
+        the individuals of every group from best to worst."""
+        from .search import decode_library
+        be = self.backend
+        lib = decode_library(be)
+        P, ne, nm, generation = int(pop), int(elite), int(mutants), int(generation)
+        if not 0.0 <= float(rho) <= 1.0:
+            raise ValueError("evolve_keys: rho must lie in [0, 1]")
+        if not 1 <= P <= _abi.EVOLVE_MAX_POP:
+            raise ValueError(f"evolve_keys: pop must lie in [1, {_abi.EVOLVE_MAX_POP}]")
+        if ne < 0 or nm < 0 or ne + nm > P or (ne + nm < P and ne < 1):
+            raise ValueError("evolve_keys: elite + mutants <= pop, and a crossover needs an elite")
+        fresh = ne == 0 and nm == P
+        with be.on_device():
+            if fresh and (isinstance(keys, (tuple, list)) and all(isinstance(x, (int, np.integer)) for x in keys)):
+                shape, k = tuple(int(x) for x in keys), None
+            else:
+                k = be.as_device(keys, "int32")
+                shape = tuple(k.shape)
+            if len(shape) < 2 or shape[0] % P or int(np.prod(shape[1:])) < 1:
+                raise ValueError(f"evolve_keys: keys must have shape (G * {P}, ...), got {shape}")
+            G, region = shape[0] // P, int(np.prod(shape[1:]))
+            fit = None
+            if not fresh:
+                if fitness is None:
+                    raise ValueError("evolve_keys: fitness is needed unless elite == 0 and mutants == pop")
+                fit = be.as_device(fitness, "int32")
+                if getattr(be, "torch", None) is None:
+                    fit = fit.copy()                                   # (as_device keeps ONE array alive)
+                if tuple(fit.shape) != (G * P,):
+                    raise ValueError(f"evolve_keys: fitness must have shape {(G * P,)}")
+            out = be.zeros(shape, "int32")
+            by_rank = be.zeros((G * P,), "int32")
+            if G:
+                p = be.ptr
+                arg = _abi.JssEvolve(G, P, region, ne, nm, int(round(float(rho) * 65536)), generation,
+                                     int(self.seed if seed is None else seed) & (2 ** 64 - 1), p(fit), p(None if fresh else k), p(out),
+                                     p(by_rank))
+                rc = lib.jss_keys_evolve(C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_keys_evolve")
+            self._evolve_keep = [k, fit]                       # alive until the launch has read them
+        return out, by_rank
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

@@ -392,6 +392,19 @@ class JssEnv(gymnasium_base("Env")):
         out = b.order_distance(None if rank is None else self._order_row(rank), self._order_row(guide))
         return int(np.asarray(b.backend.numpy(out))[0])
 
+    def decode_keys(self, keys, delta: float = 1.0, start: bool = False, info: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.decode_keys`` (include/jss_decode.h): the key table ``keys`` (J x M or jmax x mmax)
+        decoded by Giffler and Thompson's procedure with the delay parameter ``delta`` in [0, 1].  Returns the makespan, an int,
+        then with ``start`` the (jmax, mmax) start times and with ``info`` the 4 counters, host arrays."""
+        b = self._b
+        k = np.zeros((b.jmax, b.mmax), np.int32)
+        keys = np.asarray(keys)
+        k[:keys.shape[-2], :keys.shape[-1]] = keys.reshape(keys.shape[-2:])
+        out = b.decode_keys(k, None, float(delta), start, info)
+        out = out if isinstance(out, tuple) else (out,)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return int(host[0]) if len(host) == 1 else (int(host[0]),) + tuple(host[1:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

@@ -25,6 +25,11 @@ And path relinking between machine orders (include/jss_relink.h): ``relink_refer
 ``relink_library``, and ``relink_search``, the population driver: block walks whose walkers restart from a point on the path to
 their group's elite order, defined by ``tabu_blocks``, ``order_distance`` and ``relink`` (tests/relink_cases.py writes that loop
 out).
+
+And Giffler-Thompson decoding of key tables (include/jss_decode.h): ``decode_reference`` and ``evolve_reference``, the NumPy mirrors
+of ``jss_decode_keys`` and ``jss_keys_evolve``, ``rng_u32``, the libraries' counter RNG, ``decode_library``, and ``brkga_search``, a
+biased random-key genetic algorithm defined by ``decode_keys``, ``evolve_keys``, ``lower_bound`` and ``tabu_blocks``
+(tests/decode_cases.py writes that loop out).
 """
 from __future__ import annotations
 
@@ -1198,3 +1203,258 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
                         history=np.stack([host(h) for h in history], axis=1).astype(np.int32),
                         distance=np.stack([host(x) for x in distance], axis=1).astype(np.int32).reshape(S, rounds) if rounds
                         else np.zeros((S, 0), np.int32))
+
+
+# ---- Giffler-Thompson decoding of key tables, one BRKGA generation (include/jss_decode.h) ------------------------------------------
+def decode_library(backend):
+    """The library of ``backend`` that exports include/jss_decode.h: ``backend.decode_lib`` (HipBackend: libjss_decode_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
+    lib = getattr(backend, "decode_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.DECODE_SYMBOLS):
+            raise RuntimeError("decode: the backend's library does not export include/jss_decode.h")
+        _abi.bind_decode(lib)
+    return lib
+
+
+def decode_reference(env_const, ops, keys, parents=None, delta=65536, fill=-1):
+    """include/jss_decode.h's jss_decode_keys on host arrays, written from the header's definition, one candidate after the
+    other.  ``keys`` (jmax, mmax), one table for all, or (n, jmax, mmax); ``parents`` (n,) or None (candidate c is env c);
+    ``delta`` in units of 1 / 65536, an int or (n,).  Returns ``(makespan, start, info)``: int32 (n,), (n, jmax, mmax), (n, 4).  The
+    rows of refused candidates (-1) hold ``fill`` in start and info."""
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    B = const.shape[0]
+    keys = np.asarray(keys, dtype=np.int64)
+    jmax, mmax = keys.shape[-2:]
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    n = len(parents) if parents is not None else keys.shape[0] if keys.ndim == 3 else B
+    parents = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    delta = np.broadcast_to(np.asarray(delta, dtype=np.int64), (n,))
+    makespan = np.full(n, -1, np.int32)
+    start = np.full((n, jmax, mmax), fill, np.int32)
+    info = np.full((n, _abi.DECODE_NI), fill, np.int32)
+    for c in range(n):
+        i, dl = int(parents[c]), int(delta[c])
+        if not 0 <= i < B or not 0 <= dl <= 65536:
+            continue
+        J, M, tab = (int(const[i, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE))
+        if not (1 <= J <= jmax and 1 <= M <= mmax and 0 <= tab < ops.shape[0]):
+            continue
+        table = keys[c] if keys.ndim == 3 else keys
+        mach, dur = ((ops[tab] >> 16) & 63).tolist(), (ops[tab] & 0xFFFF).tolist()
+        key = table.tolist()
+        k, jobend, rel = [0] * J, [0] * J, [0] * 64
+        row = np.full((jmax, mmax), -1, np.int32)
+        conflicts = widest = delayed = 0
+        for _ in range(J * M):
+            live = [j for j in range(J) if k[j] < M]
+            est = {j: max(jobend[j], rel[mach[j][k[j]]]) for j in live}
+            ect, first = min((est[j] + dur[j][k[j]], j) for j in live)
+            m = mach[first][k[first]]
+            on_m = [j for j in live if mach[j][k[j]] == m]
+            e0 = min(est[j] for j in on_m)
+            conflict = [j for j in on_m if est[j] == e0 or (est[j] - e0) * 65536 < dl * (ect - e0)]
+            chosen = max(conflict, key=lambda j: (key[j][k[j]], -j))
+            conflicts += len(conflict) > 1
+            widest = max(widest, len(conflict))
+            delayed += est[chosen] > e0
+            row[chosen, k[chosen]] = est[chosen]
+            jobend[chosen] = rel[m] = est[chosen] + dur[chosen][k[chosen]]
+            k[chosen] += 1
+        makespan[c], start[c], info[c] = max(jobend), row, (conflicts, widest, delayed, 0)
+    return makespan, start, info
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _fmix32(x):
+    x = x & _M32
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def rng_u32(seed, env_id, episode, step):
+    """The counter RNG of the libraries (jss_common.hpp rng_u32, oracle/jss_oracle.c orc_rng_u32), vectorised over ``env_id``,
+    ``episode`` and ``step``: uint64 arrays holding 32-bit values."""
+    seed = int(seed) & (2 ** 64 - 1)
+    env_id = np.asarray(env_id, dtype=np.uint64)
+    episode = np.asarray(episode, dtype=np.int64).astype(np.uint64) & _M32
+    step = np.asarray(step, dtype=np.int64).astype(np.uint64) & _M32
+    a = (np.uint64(seed & 0xFFFFFFFF) + (env_id & _M32) * np.uint64(0x9E3779B9) + episode * np.uint64(0x85EBCA6B)
+         + step * np.uint64(0xC2B2AE35)) & _M32
+    b = np.uint64(seed >> 32) ^ (((env_id >> np.uint64(32)) * np.uint64(0x27D4EB2F)) & _M32)
+    return _fmix32(_fmix32(a) ^ b)
+
+
+def evolve_reference(keys_in, fitness, groups, pop, n_elite, n_mutant, rho_q16, generation, seed, region=None, rng=rng_u32):
+    """include/jss_decode.h's jss_keys_evolve on host arrays, written from the header's definition, one group and one child after
+    the other.  ``keys_in`` (G * P, region) and ``fitness`` (G * P,) may be None for an initial population (``n_elite == 0``,
+    ``n_mutant == pop``; ``region`` is then needed).  ``rng``: the counter RNG, ``rng(seed, row, generation, x)``.  Returns
+    ``(keys_out, by_rank)``: int32 (G * P, region) and (G * P,)."""
+    G, P = int(groups), int(pop)
+    if keys_in is not None:
+        keys_in = np.asarray(keys_in, dtype=np.int32).reshape(G * P, -1)
+        region = keys_in.shape[1]
+    region = int(region)
+    ranked = not (n_elite == 0 and n_mutant == P)
+    out = np.zeros((G * P, region), np.int32)
+    by_rank = np.zeros(G * P, np.int32)
+    key = (int(seed) ^ _abi.EVOLVE_SEED_XOR) & (2 ** 64 - 1)
+    entries = np.arange(region)
+    for g in range(G):
+        order = list(range(P))
+        if ranked:
+            fit = [int(x) for x in np.asarray(fitness).reshape(G, P)[g]]
+            order.sort(key=lambda p: (fit[p] < 0, fit[p], p))
+        by_rank[g * P:(g + 1) * P] = order
+        for c in range(P):
+            i = g * P + c
+            if c < n_elite:
+                out[i] = keys_in[g * P + order[c]]
+                continue
+            r = rng(key, i, generation, entries)
+            if c >= P - n_mutant:
+                out[i] = r.astype(np.uint32).view(np.int32)
+                continue
+            a = order[int(rng(key, i, generation, region)) % n_elite]
+            b = order[n_elite + int(rng(key, i, generation, region + 1)) % (P - n_elite)]
+            out[i] = np.where((r >> np.uint64(16)) < np.uint64(rho_q16), keys_in[g * P + a], keys_in[g * P + b])
+    return out, by_rank
+
+
+@dataclass
+class BrkgaResult:
+    """What ``brkga_search`` returns, host arrays.  Per instance: ``makespan`` (G,); ``keys`` (G, jmax, mmax), the key table of the
+    individual that gave it; ``start`` (G, jmax, mmax), the start times of its schedule; ``rank`` (G, jmax, mmax), its machine
+    order (the decoded start times, or with ``polish`` the positions the block walk returned); ``history`` (G, generations + 1),
+    the group's best decoded makespan of every population; ``generations``, the generations made; ``optimal`` (G,): the makespan
+    reached the target, a lower bound; ``env`` the batch of G envs."""
+    makespan: np.ndarray
+    keys: np.ndarray
+    start: np.ndarray
+    rank: np.ndarray
+    history: np.ndarray
+    generations: int
+    optimal: np.ndarray
+    env: Optional[BatchedJssEnv] = None
+
+
+def brkga_search(instances, population=256, generations=100, elite=0.15, mutants=0.15, rho=0.7, delta=0.5, seed_rules=("SPT", "MWR"),
+                 polish=0, tenure=8, seed=0, target="lower_bound", check_every=8, device=None, _backend=None):
+    """A biased random-key genetic algorithm over per-operation priority keys, decoded by Giffler and Thompson's procedure, on
+    one instance or on a list of them: one group of ``population`` individuals per instance and ONE batch of one env per
+    instance, which is only read (``parents = repeat(arange(G), P)``).  Defined by public calls alone:
+
+    start   the batch, ``reset``, the target (``"lower_bound"``: ``env.lower_bound()`` of the reset state; None; an int or one
+            per instance); population 0 is ``evolve_keys((G * P, jmax, mmax), None, P, 0, P, generation=0, seed=seed)``, the
+            first individuals of every group overwritten by ``dispatching.rule_keys(instance, rule)`` for ``seed_rules`` (padding 0).
+    generation t = 1 ...  ``fitness = decode_keys(keys, parents, delta)`` then ``keys = evolve_keys(keys, fitness, P, n_elite,
+            n_mutant, rho, generation=t, seed=seed)`` with ``n_elite = max(1, round(elite * P))`` and ``n_mutant = round(mutants *
+            P)``.  Nothing is computed by the host and nothing comes to it, but every ``check_every`` generations the
+            groups' minima of that window: the search ends once every group is at or below its target, or after ``generations``.
+            Elites are copied, so a group's best never rises.
+    end     one more ``decode_keys`` of the last population, with its start times.  ``polish == 0``: the result is the lowest
+            ``(makespan, individual)`` of every group, ``rank`` its start times.  ``polish > 0``: every individual's start
+            times are the rank of one walker of ``tabu_blocks(rank=start, iters=polish, tenure=tenure)`` on a batch of G * P
+            envs, and the result is the lowest ``(best_makespan, individual)`` of every group.
+
+    Returns a ``BrkgaResult``."""
+    from .dispatching import rule_keys
+    P, gens, polish, check_every = int(population), int(generations), int(polish), int(check_every)
+    if not 1 <= P <= _abi.EVOLVE_MAX_POP:
+        raise ValueError(f"brkga_search: population must lie in [1, {_abi.EVOLVE_MAX_POP}]")
+    if gens < 0 or polish < 0 or check_every < 1:
+        raise ValueError("brkga_search: generations >= 0, polish >= 0, check_every >= 1")
+    if not (0.0 <= float(rho) <= 1.0 and 0.0 <= float(delta) <= 1.0 and 0.0 <= float(elite) <= 1.0 and 0.0 <= float(mutants) <= 1.0):
+        raise ValueError("brkga_search: rho, delta, elite and mutants lie in [0, 1]")
+    n_elite, n_mutant = max(1, int(round(float(elite) * P))), int(round(float(mutants) * P))
+    if n_elite + n_mutant > P:
+        raise ValueError("brkga_search: elite + mutants must not exceed the population")
+    if not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
+        raise ValueError(f"brkga_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}]")
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError("brkga_search takes instances (a name, a path, an Instance, or a list of them): call decode_keys "
+                                  "and evolve_keys on a BatchedJssEnv for anything else")
+    one = isinstance(instances, (str, os.PathLike, Instance))
+    names = [instances] if one else list(instances)
+    G = len(names)
+    if G < 1:
+        raise ValueError("brkga_search: need at least one instance")
+    rules = tuple(seed_rules or ())
+    if len(rules) > P:
+        raise ValueError("brkga_search: more seed rules than individuals")
+    if isinstance(target, str) and target != "lower_bound":
+        raise ValueError("brkga_search: target is 'lower_bound', None, an int or one int per instance")
+    S = G * P
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+
+    def batch(per_group):
+        if G == 1:
+            return BatchedJssEnv(names[0], batch=per_group, seed=int(seed or 0), **kw)
+        return BatchedJssEnv(names, batch=G * per_group, table_of_env=np.repeat(np.arange(G), per_group), order="interleaved",
+                             seed=int(seed or 0), **kw)
+
+    env = batch(1)
+    be = env.backend
+    env.reset()
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    if isinstance(target, str):
+        tgt = host(env.lower_bound()).astype(np.int32)
+    elif target is None:
+        tgt = None
+    else:
+        tgt = np.broadcast_to(np.asarray(target, np.int32), (G,)).copy()
+    jmax, mmax = env.jmax, env.mmax
+    xp = be.torch if getattr(be, "torch", None) is not None else np
+    never = 2 ** 31 - 1
+    with be.on_device():
+        parents = be.from_numpy(np.repeat(np.arange(G), P).astype(np.int32))
+        keys, _ = env.evolve_keys((S, jmax, mmax), None, P, 0, P, rho, 0, seed)
+        if rules:
+            seeds = np.zeros((G, len(rules), jmax, mmax), np.int32)
+            for g, name in enumerate(names):
+                for r, rule in enumerate(rules):
+                    table = rule_keys(name, rule)
+                    seeds[g, r, :table.shape[0], :table.shape[1]] = table
+            keys.reshape(G, P, jmax, mmax)[:, :len(rules)] = be.from_numpy(seeds)
+
+        def group_low(mk):                                           # (G,): an individual without a schedule counts as +inf
+            low = xp.where(mk >= 0, mk, never).reshape(G, P).min(1)
+            return low if xp is np else low.values
+
+        history, t = [], 0
+        while True:
+            fitness = env.decode_keys(keys, parents, delta)
+            history.append(group_low(fitness))
+            if t == gens:
+                break
+            if tgt is not None and t and t % check_every == 0:
+                window = np.stack([host(h) for h in history[-check_every:]], axis=1)
+                if (window.min(axis=1) <= tgt).all():
+                    break
+            t += 1
+            keys, _ = env.evolve_keys(keys, fitness, P, n_elite, n_mutant, rho, t, seed)
+        fitness, start = env.decode_keys(keys, parents, delta, start=True)
+    mk = host(fitness).astype(np.int32)
+    if polish:
+        walkers = batch(P)
+        walkers.reset()
+        best, rank, _ = walkers.tabu_blocks(start, polish, int(tenure))
+        mk = host(best).astype(np.int32)
+    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, P)
+    winner = (np.arange(G) * P + by_group.argmin(axis=1)).astype(np.int32)   # (the first of equal makespans)
+    if polish:
+        again, begin = walkers.evaluate_order(rank, winner, start=True)
+        assert np.array_equal(host(again), mk[winner])
+        rank_out, start_out = host(rank)[winner].copy(), host(begin).copy()
+    else:
+        start_out = host(start)[winner].copy()
+        rank_out = start_out.copy()
+    return BrkgaResult(makespan=mk[winner], keys=host(keys)[winner].copy(), start=start_out, rank=rank_out,
+                       history=np.stack([host(h) for h in history], axis=1).astype(np.int32), generations=t,
+                       optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, env=env)

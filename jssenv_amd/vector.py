@@ -120,6 +120,14 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
                                   "(search.relink_search takes a list of instances)")
 
+    def decode_keys(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not decode key tables: call decode_keys on a BatchedJssEnv "
+                                  "(search.brkga_search takes a list of instances)")
+
+    def evolve_keys(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
+                                  "(search.brkga_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
