@@ -135,6 +135,14 @@ DECODE_NI = 4                     # info row: conflicts, widest, delayed, 0
 EVOLVE_SEED_XOR = 0xD1B54A32D192ED03   # keys jss_keys_evolve's counter RNG: rng_u32(seed ^ EVOLVE_SEED_XOR, row, generation, x)
 EVOLVE_MAX_POP = 4096
 
+# include/jss_machine.h: the companion header of the one-machine relaxations of partial selections and of the shifting bottleneck
+# construction (its own version).  The HIP library exports both from a ninth library, libjss_machine_hip.so; the twin from
+# libjss_cpu.so.
+MACHINE_VERSION = 1
+MACHINE_SYMBOLS = ("jss_machine_relax", "jss_bottleneck_build")
+BOTTLENECK_NI = 4                 # info row: machines fixed, re-sequencings tried, re-sequencings that shortened, first bound
+BOTTLENECK_MAX_REOPT = 8
+
 _p = C.c_void_p
 
 
@@ -238,6 +246,16 @@ class JssEvolve(C.Structure):        # include/jss_decode.h
     _fields_ = [("groups", C.c_int32), ("pop", C.c_int32), ("region", C.c_int32), ("n_elite", C.c_int32), ("n_mutant", C.c_int32),
                 ("rho_q16", C.c_int32), ("generation", C.c_int32), ("seed", C.c_uint64), ("fitness", _p), ("keys_in", _p),
                 ("keys_out", _p), ("by_rank", _p)]
+
+
+class JssMachineRelax(C.Structure):  # include/jss_machine.h
+    _fields_ = [("n", C.c_int32), ("stride", C.c_int32), ("parents", _p), ("rank", _p), ("fixed", _p), ("length", _p),
+                ("lower_bound", _p), ("bottleneck", _p), ("jps", _p), ("schrage", _p), ("head", _p), ("tail", _p), ("rank_out", _p)]
+
+
+class JssBottleneck(C.Structure):    # include/jss_machine.h
+    _fields_ = [("n", C.c_int32), ("reopt", C.c_int32), ("parents", _p), ("rank_in", _p), ("fixed_in", _p), ("bias", _p),
+                ("makespan", _p), ("rank", _p), ("info", _p), ("order", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -410,6 +428,18 @@ def bind_decode(lib):
     lib.jss_decode_keys.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssDecode), _p]
     lib.jss_keys_evolve.restype = C.c_int
     lib.jss_keys_evolve.argtypes = [C.POINTER(JssEvolve), _p]
+    return lib
+
+
+def bind_machine(lib):
+    """Attach the prototypes of include/jss_machine.h; raises AttributeError naming the first missing symbol."""
+    for name in MACHINE_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_machine_relax.restype = C.c_int
+    lib.jss_machine_relax.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssMachineRelax), _p]
+    lib.jss_bottleneck_build.restype = C.c_int
+    lib.jss_bottleneck_build.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBottleneck), _p]
     return lib
 
 

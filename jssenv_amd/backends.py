@@ -52,6 +52,7 @@ class HipBackend:
         self._block_lib = None
         self._relink_lib = None
         self._decode_lib = None
+        self._machine_lib = None
 
     @property
     def beam_lib(self):
@@ -122,6 +123,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_decode_extension)")
             self._decode_lib = _abi.bind_decode(C.CDLL(path))
         return self._decode_lib
+
+    @property
+    def machine_lib(self):
+        """libjss_machine_hip.so (include/jss_machine.h), loaded on first use; a missing library is an error."""
+        if self._machine_lib is None:
+            path = _abi.library_path("libjss_machine_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_machine_extension)")
+            self._machine_lib = _abi.bind_machine(C.CDLL(path))
+        return self._machine_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -345,6 +356,11 @@ class CpuBackend:
     def decode_lib(self):
         """the library that exports include/jss_decode.h: the twin itself"""
         return _abi.bind_decode(self.lib)
+
+    @property
+    def machine_lib(self):
+        """the library that exports include/jss_machine.h: the twin itself"""
+        return _abi.bind_machine(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -238,6 +238,14 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
                                   "(search.brkga_search takes a list of instances)")
 
+    def relax_machines(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not relax partial selections: call relax_machines on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
+    def bottleneck(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

@@ -20,6 +20,7 @@
 #include "jss_block.h"
 #include "jss_relink.h"
 #include "jss_decode.h"
+#include "jss_machine.h"
 
 namespace jss_abi {
 
@@ -460,6 +461,34 @@ inline int evolve_check(const JssEvolve *e) {
     if (!all_mutants && (!e->fitness || !e->keys_in)) return JSS_E_NULL;
     if (e->keys_out == e->keys_in) return JSS_E_NULL;
     return 0;
+}
+
+// ---- one-machine relaxations and the shifting bottleneck construction (include/jss_machine.h) ---------------------------------
+// What libjss_machine_hip.so keeps in LDS for one candidate, for the whole call: the op row, the rank row, the heads, the tails
+// and a scratch row (int32) and two rows of machine-sorted sequences (uint16) over the entries of a [jmax][mmax] row rounded up
+// to a multiple of 8, and four blocks of one word per machine.
+inline long long machine_lds_bytes(int jmax, int mmax) { return 24 * order_entries8(jmax, mmax) + 4 * 64 * 4; }
+
+// jss_machine_relax (libjss_machine_hip.so and the twin): the batch as jss_order_eval checks it
+inline int machine_relax_check(const JssDesc *d, const JssState *s, const JssMachineRelax *r) {
+    if (!d || !s || !r) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!r->length || (!r->rank && r->fixed) || (r->rank_out && r->rank_out == r->rank)) return JSS_E_NULL;
+    if (r->n < 0 || (!r->parents && r->n != d->batch)) return JSS_E_SHAPE;
+    if (r->stride != 0 && r->stride != d->jmax * d->mmax) return JSS_E_SHAPE;
+    return machine_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// jss_bottleneck_build (libjss_machine_hip.so and the twin)
+inline int bottleneck_check(const JssDesc *d, const JssState *s, const JssBottleneck *b) {
+    if (!d || !s || !b) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!b->makespan || !b->rank || !b->rank_in != !b->fixed_in || b->rank == b->rank_in) return JSS_E_NULL;
+    if (b->n < 0 || (!b->parents && b->n != d->batch)) return JSS_E_SHAPE;
+    if (b->reopt < 0 || b->reopt > JSS_BOTTLENECK_MAX_REOPT) return JSS_E_SHAPE;
+    return machine_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -2163,3 +2163,240 @@ int jss_keys_evolve(const JssEvolve *evolve, void *) {
 }
 
 }  // extern "C"
+
+// ---- one-machine relaxations of partial selections, the shifting bottleneck construction (include/jss_machine.h) ---------------
+namespace {
+
+// One candidate's instance, and the header's definitions on it: the graph of a partial selection walked in topological order,
+// Jackson's preemptive schedule and Schrage's schedule by scans over a machine's operations.
+struct MachineProblem {
+    int J = 0, M = 0, mmax = 0;
+    const int32_t *ops = nullptr;
+    std::vector<int> on[JSS_MAX_MACHINES];       // a machine's real operations, flat indices ascending
+    std::vector<int32_t> head, tail;
+    std::vector<int> before, behind, waits, topo;
+
+    // false: refused (the parent, the env, the mask)
+    bool open(const JssDesc &d, const JssState *state, int parent, uint64_t fixed) {
+        if (parent < 0 || parent >= d.batch) return false;
+        const int32_t *ec = state->env_const + (size_t)parent * JSS_NC;
+        J = ec[JSS_C_JOBS], M = ec[JSS_C_MACHINES], mmax = d.mmax;
+        const int tab = ec[JSS_C_TABLE];
+        if (J < 1 || J > d.jmax || M < 1 || M > d.mmax || tab < 0 || tab >= d.n_tables) return false;
+        if (M < 64 && (fixed >> M)) return false;
+        const size_t region = (size_t)d.jmax * d.mmax;
+        ops = d.ops + (size_t)tab * region;
+        head.assign(region, 0), tail.assign(region, 0), before.assign(region, -1), behind.assign(region, -1), waits.assign(region, 0);
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) on[mach(j * mmax + k)].push_back(j * mmax + k);
+        return true;
+    }
+    int mach(int x) const { return (ops[x] >> 16) & 63; }
+    int dur(int x) const { return ops[x] & kDurMask; }
+    uint64_t used() const {
+        uint64_t u = 0;
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) u |= (uint64_t)!on[m].empty() << m;
+        return u;
+    }
+    bool negative_rank(const int32_t *rank, uint64_t fixed) const {
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m)
+            if (fixed >> m & 1)
+                for (int x : on[m])
+                    if (rank[x] < 0) return true;
+        return false;
+    }
+    // heads, tails and the length of (rank, fixed); -2: cyclic
+    int relax(const int32_t *rank, uint64_t fixed) {
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) {
+            std::vector<int> seq = on[m];
+            if (fixed >> m & 1) std::sort(seq.begin(), seq.end(), [&](int x, int y) { return rank[x] != rank[y] ? rank[x] < rank[y] : x < y; });
+            for (size_t i = 0; i < seq.size(); ++i) {
+                const bool tied = fixed >> m & 1;
+                before[seq[i]] = tied && i > 0 ? seq[i - 1] : -1;
+                behind[seq[i]] = tied && i + 1 < seq.size() ? seq[i + 1] : -1;
+            }
+        }
+        topo.clear();
+        for (int j = 0; j < J; ++j)
+            for (int k = 0; k < M; ++k) {
+                const int x = j * mmax + k;
+                waits[x] = (k > 0) + (before[x] >= 0);
+                if (!waits[x]) topo.push_back(x);
+            }
+        for (size_t i = 0; i < topo.size(); ++i) {
+            const int x = topo[i], k = x % mmax;
+            if (k + 1 < M && !--waits[x + 1]) topo.push_back(x + 1);
+            if (behind[x] >= 0 && !--waits[behind[x]]) topo.push_back(behind[x]);
+        }
+        if ((int)topo.size() < J * M) return -2;
+        int length = 0;
+        for (int x : topo) {
+            const int k = x % mmax;
+            int h = k > 0 ? head[x - 1] + dur(x - 1) : 0;
+            if (before[x] >= 0) h = std::max(h, head[before[x]] + dur(before[x]));
+            head[x] = h, length = std::max(length, h + dur(x));
+        }
+        for (size_t i = topo.size(); i-- > 0;) {
+            const int x = topo[i], k = x % mmax;
+            int t = k + 1 < M ? dur(x + 1) + tail[x + 1] : 0;
+            if (behind[x] >= 0) t = std::max(t, dur(behind[x]) + tail[behind[x]]);
+            tail[x] = t;
+        }
+        return length;
+    }
+    int jackson(int m) const {
+        const std::vector<int> &its = on[m];
+        const int n = (int)its.size();
+        std::vector<int> rem((size_t)n);
+        int t = INT32_MAX, left = n, value = 0;
+        for (int i = 0; i < n; ++i) rem[i] = dur(its[i]), t = std::min(t, head[its[i]]);
+        while (left) {
+            int pick = -1, later = INT32_MAX;
+            for (int i = 0; i < n; ++i) {
+                if (rem[i] < 0) continue;
+                if (head[its[i]] > t) later = std::min(later, head[its[i]]);
+                else if (pick < 0 || tail[its[i]] > tail[its[pick]]) pick = i;
+            }
+            if (pick < 0) {
+                t = later;
+                continue;
+            }
+            const int run = later == INT32_MAX ? rem[pick] : std::min(rem[pick], later - t);
+            t += run;
+            if (run == rem[pick]) rem[pick] = -1, --left, value = std::max(value, t + tail[its[pick]]);
+            else rem[pick] -= run;
+        }
+        return value;
+    }
+    // the starts go to rank_out[flat index] where given
+    int schrage(int m, int32_t *rank_out) const {
+        const std::vector<int> &its = on[m];
+        const int n = (int)its.size();
+        std::vector<char> done((size_t)n, 0);
+        int t = INT32_MAX, left = n, value = 0;
+        for (int i = 0; i < n; ++i) t = std::min(t, head[its[i]]);
+        while (left) {
+            int pick = -1, later = INT32_MAX;
+            for (int i = 0; i < n; ++i) {
+                if (done[i]) continue;
+                if (head[its[i]] > t) later = std::min(later, head[its[i]]);
+                else if (pick < 0 || tail[its[i]] > tail[its[pick]]) pick = i;
+            }
+            if (pick < 0) {
+                t = later;
+                continue;
+            }
+            const int x = its[pick];
+            if (rank_out) rank_out[x] = t;
+            value = std::max(value, t + dur(x) + tail[x]);
+            t += dur(x), done[pick] = 1, --left;
+        }
+        return value;
+    }
+    // -1 in the padding of a [jmax][mmax] row, `of` elsewhere
+    void write_row(int32_t *out, int jmax, const int32_t *of) const {
+        for (int j = 0; j < jmax; ++j)
+            for (int k = 0; k < mmax; ++k) out[j * mmax + k] = j < J && k < M ? of[j * mmax + k] : -1;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int jss_machine_relax(const JssDesc *desc, const JssState *state, const JssMachineRelax *relax, void *) {
+    if (const int rc = machine_relax_check(desc, state, relax)) return rc;
+    const JssDesc d = *desc;
+    const JssMachineRelax t = *relax;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int c) {
+        const uint64_t fixed = t.fixed ? t.fixed[c] : 0;
+        const int32_t *rank = t.rank ? t.rank + (size_t)c * t.stride : nullptr;
+        MachineProblem w;
+        if (!w.open(d, state, t.parents ? t.parents[c] : c, fixed) || w.negative_rank(rank, fixed)) return void(t.length[c] = -1);
+        const int length = w.relax(rank, fixed);
+        t.length[c] = length;
+        if (length < 0) return;
+        std::vector<int32_t> row((size_t)region, 0);
+        if (rank) std::copy(rank, rank + region, row.begin());
+        int best = -1, neck = -1;
+        for (int m = 0; m < mmax; ++m) {
+            const bool open = !(fixed >> m & 1) && !w.on[m].empty();
+            const int jps = open ? w.jackson(m) : -1, sch = open ? w.schrage(m, row.data()) : -1;
+            if (t.jps) t.jps[(size_t)c * mmax + m] = jps;
+            if (t.schrage) t.schrage[(size_t)c * mmax + m] = sch;
+            if (jps > best) best = jps, neck = m;
+        }
+        if (t.lower_bound) t.lower_bound[c] = std::max(length, best);
+        if (t.bottleneck) t.bottleneck[c] = neck;
+        if (t.head) w.write_row(t.head + (size_t)c * region, d.jmax, w.head.data());
+        if (t.tail) w.write_row(t.tail + (size_t)c * region, d.jmax, w.tail.data());
+        if (t.rank_out) w.write_row(t.rank_out + (size_t)c * region, d.jmax, row.data());
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+int jss_bottleneck_build(const JssDesc *desc, const JssState *state, const JssBottleneck *build, void *) {
+    if (const int rc = bottleneck_check(desc, state, build)) return rc;
+    const JssDesc d = *desc;
+    const JssBottleneck t = *build;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int c) {
+        uint64_t fixed = t.fixed_in ? t.fixed_in[c] : 0;
+        std::vector<int32_t> rank((size_t)region, 0), saved;
+        if (t.rank_in) std::copy(t.rank_in + (size_t)c * region, t.rank_in + (size_t)(c + 1) * region, rank.begin());
+        MachineProblem w;
+        if (!w.open(d, state, t.parents ? t.parents[c] : c, fixed) || w.negative_rank(rank.data(), fixed)) return void(t.makespan[c] = -1);
+        const uint64_t used = w.used();
+        int length = w.relax(rank.data(), fixed);
+        int first = length, n_fixed = 0, tried = 0, shorter = 0, order[JSS_MAX_MACHINES];
+        bool at_start = true;
+        while (length >= 0 && (used & ~fixed)) {
+            int star = -1;
+            long long high = 0;
+            for (int m = 0; m < mmax; ++m) {
+                if (!(used & ~fixed & (1ull << m))) continue;
+                const int jps = w.jackson(m);
+                if (at_start) first = std::max(first, jps);
+                const long long v = (long long)jps + (t.bias ? t.bias[(size_t)c * mmax + m] : 0);
+                if (star < 0 || v > high) star = m, high = v;
+            }
+            at_start = false;
+            w.schrage(star, rank.data());
+            fixed |= 1ull << star, order[n_fixed++] = star;
+            int cur = length = w.relax(rank.data(), fixed);
+            if (cur < 0) break;
+            for (int round = 0; round < t.reopt; ++round)
+                for (int k = 0; k < JSS_MAX_MACHINES; ++k) {
+                    if (!(fixed >> k & 1) || k == star) continue;
+                    ++tried;                                            // (a fixed machine without operations: nothing changes)
+                    if (w.on[k].empty()) continue;
+                    w.relax(rank.data(), fixed & ~(1ull << k));
+                    saved.clear();
+                    for (int x : w.on[k]) saved.push_back(rank[x]);
+                    w.schrage(k, rank.data());
+                    const int now = w.relax(rank.data(), fixed);
+                    if (now >= 0 && now <= cur) {
+                        shorter += now < cur, cur = now;
+                    } else {
+                        for (size_t i = 0; i < saved.size(); ++i) rank[w.on[k][i]] = saved[i];
+                    }
+                }
+            length = w.relax(rank.data(), fixed);
+        }
+        t.makespan[c] = length;
+        if (length < 0) return;
+        w.write_row(t.rank + (size_t)c * region, d.jmax, rank.data());
+        if (t.info) {
+            int32_t *row = t.info + (size_t)c * JSS_BOTTLENECK_NI;
+            row[0] = n_fixed, row[1] = tried, row[2] = shorter, row[3] = first;
+        }
+        if (t.order)
+            for (int m = 0; m < mmax; ++m) t.order[(size_t)c * mmax + m] = m < n_fixed ? order[m] : -1;
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+}  // extern "C"

@@ -1232,6 +1232,155 @@ class BatchedJssEnv:
             self._evolve_keep = [k, fit]                       # alive until the launch has read them
         return out, by_rank
 
+    # -- one-machine relaxations of partial selections, the shifting bottleneck construction (include/jss_machine.h) ------------
+    def _fixed_masks(self, fixed, n, what):
+        """``fixed`` -- an int, ``(n,)`` integers or a boolean ``(n, M)`` array -- as ``(n,)`` uint64 machine masks on the host"""
+        if hasattr(fixed, "detach"):
+            fixed = fixed.detach().cpu().numpy()
+        if isinstance(fixed, (int, np.integer)):
+            if not 0 <= int(fixed) < 2 ** 64:
+                raise ValueError(f"{what}: fixed must be a 64-bit machine mask")
+            return np.full(n, int(fixed), np.uint64)
+        a = np.asarray(fixed)
+        if a.dtype == np.bool_:
+            if a.ndim != 2 or a.shape[0] != n or a.shape[1] > 64:
+                raise ValueError(f"{what}: a boolean fixed must have shape ({n}, M)")
+            return (a.astype(np.uint64) << np.arange(a.shape[1], dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+        if a.dtype.kind not in "iu" or a.shape != (n,):
+            raise ValueError(f"{what}: fixed must be an int, {(n,)} integers or a boolean ({n}, M) array")
+        if a.dtype.kind == "i" and (a < 0).any() and a.dtype != np.int64:      # (a negative int64 is a mask with bit 63 set)
+            raise ValueError(f"{what}: fixed must not be negative")
+        return a.astype(np.int64).view(np.uint64) if a.dtype.kind == "i" else a.astype(np.uint64)
+
+    def _machine_call_start(self, what, parents, tables, fixed):
+        """what relax_machines and bottleneck have in common: the checks, the parents on the device, n"""
+        if not self._is_reset:
+            raise RuntimeError(f"call reset() before {what}()")
+        if self._session is not None and not self._session.closed:
+            raise NotImplementedError(f"{what} does not run while a step session is open on this env: close() it first")
+        be = self.backend
+        par = None
+        if parents is not None:
+            par = be.as_device(parents, "int32")
+            if getattr(be, "torch", None) is None:
+                par = par.copy()                                       # (as_device keeps ONE array alive)
+            if len(par.shape) != 1:
+                raise ValueError(f"{what}: parents must have shape (n,)")
+        fixed_n = None
+        if fixed is not None and not isinstance(fixed, (int, np.integer)):
+            fixed_n = int(fixed.shape[0]) if hasattr(fixed, "shape") else len(fixed)
+        n = int(par.shape[0]) if par is not None else tables if tables is not None else fixed_n if fixed_n is not None else self.batch
+        if par is None and n != self.batch:
+            raise ValueError(f"{what}: without parents there is one candidate per env ({self.batch}), got {n}")
+        return par, n
+
+    def relax_machines(self, rank=None, fixed=0, parents=None, jps: bool = False, schrage: bool = False, head: bool = False,
+                       tail: bool = False, rank_out: bool = False):
+        """The one-machine relaxations of a partial selection, one per candidate in one launch (include/jss_machine.h defines
+        them; integers, the same bits on every backend).  Candidate c looks at the instance of env ``parents[c]`` (``None``: env
+        c, and n == B).  ``fixed`` says which machines are sequenced: an int (one mask for all, bit m for machine m), ``(n,)``
+        integers or a boolean ``(n, M)`` array; ``rank`` is int32 ``(jmax, mmax)`` -- one table for all -- or ``(n, jmax, mmax)``
+        and orders the operations of the fixed machines as in ``evaluate_order``; it may be None while nothing is fixed.  Only
+        the instance tables are read.
+
+        Returns ``(lower_bound, length, bottleneck)``, each (n,) int32: ``length`` the longest path of the partial selection (-1
+        refused, -2 cyclic), ``lower_bound`` the larger of it and the free machines' Jackson preemptive bounds, ``bottleneck``
+        the free machine with the largest one (-1: none is free).  Then, each where asked for and in this order: ``jps`` and
+        ``schrage`` (n, mmax), -1 for fixed and unused machines; ``head`` and ``tail`` (n, jmax, mmax); ``rank_out`` (n, jmax,
+        mmax): ``rank`` with the free machines' operations at their Schrage starts, so that one more bit of ``fixed`` sequences
+        that machine.  Arrays of the env's backend."""
+        from .search import machine_library
+        be = self.backend
+        lib = machine_library(be)
+        B, region = self.batch, self.jmax * self.mmax
+        with be.on_device():
+            r, shape = None, None
+            if rank is not None:
+                r = be.as_device(rank, "int32")
+                shape = tuple(r.shape)
+                if not (shape == (self.jmax, self.mmax) or (len(shape) == 3 and shape[1:] == (self.jmax, self.mmax))):
+                    raise ValueError(f"relax_machines: rank must have shape {(self.jmax, self.mmax)} or (n, {self.jmax}, {self.mmax}), got {shape}")
+            par, n = self._machine_call_start("relax_machines", parents, shape[0] if shape and len(shape) == 3 else None, fixed)
+            if shape and len(shape) == 3 and shape[0] != n:
+                raise ValueError(f"relax_machines: {shape[0]} rank tables for {n} candidates")
+            masks = self._fixed_masks(fixed, n, "relax_machines")
+            if r is None and masks.any():
+                raise ValueError("relax_machines: a fixed machine needs a rank")
+            fx = be.from_numpy(masks.view(np.int64)) if masks.any() else None
+
+            def out(*shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            length, lower, neck = out(n), out(n), out(n)
+            rows = [out(n, self.mmax) if jps else None, out(n, self.mmax) if schrage else None] + \
+                   [out(n, self.jmax, self.mmax) if want else None for want in (head, tail, rank_out)]
+            if n:
+                p = be.ptr
+                arg = _abi.JssMachineRelax(n, region if shape and len(shape) == 3 else 0, p(par), p(r), p(fx), p(length), p(lower), p(neck),
+                                           *(p(x) for x in rows))
+                rc = lib.jss_machine_relax(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_machine_relax")
+            self._machine_keep = [r, par, fx]                  # alive until the launch has read them
+        return (lower, length, neck) + tuple(x for x in rows if x is not None)
+
+    def bottleneck(self, parents=None, bias=None, reopt: int = 1, rank=None, fixed=None, order: bool = False):
+        """A shifting bottleneck construction per candidate, all in one launch (``jss_bottleneck_build``, include/jss_machine.h;
+        integers, the same bits on every backend): relax, sequence the machine with the largest Jackson preemptive bound by
+        Schrage's schedule, re-sequence every machine fixed before ``reopt`` times (in [0, 8]), until every machine is
+        sequenced.  Candidate c builds on the instance of env ``parents[c]`` (``None``: env c, and n == B).  ``bias`` is int32
+        ``(n, mmax)`` or None: added to the machines' bounds when the bottleneck is chosen, so that candidates of one instance
+        build different schedules.  ``rank`` (n, jmax, mmax) and ``fixed`` (as in ``relax_machines``), given together, let a
+        build go on from a partial selection.  Only the instance tables are read.
+
+        Returns ``(makespan, rank, info)``: (n,) int32 (-1 refused, -2 a selection turned cyclic, which durations of 0 can
+        cause), the (n, jmax, mmax) machine orders (a rank tensor for ``evaluate_order``, ``tabu_blocks`` and ``relink``) and the
+        (n, 4) counters (machines fixed, re-sequencings tried, re-sequencings that shortened the schedule, the lower bound of the
+        first relaxation); with ``order`` also the (n, mmax) machines in the order they were fixed, -1 behind them."""
+        from .search import machine_library
+        be = self.backend
+        lib = machine_library(be)
+        if not 0 <= int(reopt) <= _abi.BOTTLENECK_MAX_REOPT:
+            raise ValueError(f"bottleneck: reopt must lie in [0, {_abi.BOTTLENECK_MAX_REOPT}]")
+        if (rank is None) != (fixed is None):
+            raise ValueError("bottleneck: rank and fixed are given together")
+        with be.on_device():
+            r = None
+            if rank is not None:
+                r = be.as_device(rank, "int32")
+                if len(r.shape) != 3 or tuple(r.shape[1:]) != (self.jmax, self.mmax):
+                    raise ValueError(f"bottleneck: rank must have shape (n, {self.jmax}, {self.mmax}), got {tuple(r.shape)}")
+            par, n = self._machine_call_start("bottleneck", parents, int(r.shape[0]) if r is not None else None, fixed)
+            if r is not None and int(r.shape[0]) != n:
+                raise ValueError(f"bottleneck: {int(r.shape[0])} rank tables for {n} candidates")
+            fx = None if fixed is None else be.from_numpy(self._fixed_masks(fixed, n, "bottleneck").view(np.int64))
+            bs = None
+            if bias is not None:
+                bs = be.as_device(bias, "int32")
+                if getattr(be, "torch", None) is None:
+                    bs = bs.copy()
+                if tuple(bs.shape) != (n, self.mmax):
+                    raise ValueError(f"bottleneck: bias must have shape {(n, self.mmax)}, got {tuple(bs.shape)}")
+            mk = be.zeros((n,), "int32")
+            mk -= 1
+            out = be.zeros((n, self.jmax, self.mmax), "int32")
+            out -= 1
+            info = be.zeros((n, _abi.BOTTLENECK_NI), "int32")
+            fixed_order = None
+            if order:
+                fixed_order = be.zeros((n, self.mmax), "int32")
+                fixed_order -= 1
+            if n:
+                p = be.ptr
+                arg = _abi.JssBottleneck(n, int(reopt), p(par), p(r), p(fx), p(bs), p(mk), p(out), p(info), p(fixed_order))
+                rc = lib.jss_bottleneck_build(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_bottleneck_build")
+            self._machine_keep = [r, par, fx, bs]              # alive until the launch has read them
+        return (mk, out, info, fixed_order) if order else (mk, out, info)
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

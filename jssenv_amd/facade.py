@@ -405,6 +405,35 @@ class JssEnv(gymnasium_base("Env")):
         host = [np.asarray(b.backend.numpy(x))[0] for x in out]
         return int(host[0]) if len(host) == 1 else (int(host[0]),) + tuple(host[1:])
 
+    def _machine_row(self, rank):
+        """a J x M or jmax x mmax table as the (1, jmax, mmax) int32 rank of the batch of one"""
+        b = self._b
+        row = np.zeros((1, b.jmax, b.mmax), np.int32)
+        rank = np.asarray(rank)
+        row[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
+        return row
+
+    def relax_machines(self, rank=None, fixed: int = 0, jps: bool = False, schrage: bool = False, head: bool = False, tail: bool = False,
+                       rank_out: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.relax_machines`` (include/jss_machine.h): the one-machine relaxations of the partial
+        selection in which the machines of the mask ``fixed`` are sequenced by ``rank`` (J x M or jmax x mmax; None while nothing
+        is fixed).  Returns ``(lower_bound, length, bottleneck)``, ints, then each where asked for ``jps``, ``schrage`` (mmax,),
+        ``head``, ``tail`` and ``rank_out`` (jmax, mmax), host arrays."""
+        b = self._b
+        out = b.relax_machines(None if rank is None else self._machine_row(rank), int(fixed), None, jps, schrage, head, tail, rank_out)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return tuple(int(x) for x in host[:3]) + tuple(host[3:])
+
+    def bottleneck(self, bias=None, reopt: int = 1, rank=None, fixed=None, order: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.bottleneck`` (include/jss_machine.h): one shifting bottleneck construction, from
+        nothing or from the partial selection ``(rank, fixed)``; ``bias`` (mmax,) is added to the machines' bounds when the
+        bottleneck is chosen.  Returns ``(makespan, rank, info[, order])``: an int (-1 refused, -2 cyclic) and host arrays."""
+        b = self._b
+        out = b.bottleneck(None, None if bias is None else np.asarray(bias, np.int32).reshape(1, -1), reopt,
+                           None if rank is None else self._machine_row(rank), None if fixed is None else int(fixed), order)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return (int(host[0]),) + tuple(host[1:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

@@ -30,6 +30,12 @@ And Giffler-Thompson decoding of key tables (include/jss_decode.h): ``decode_ref
 of ``jss_decode_keys`` and ``jss_keys_evolve``, ``rng_u32``, the libraries' counter RNG, ``decode_library``, and ``brkga_search``, a
 biased random-key genetic algorithm defined by ``decode_keys``, ``evolve_keys``, ``lower_bound`` and ``tabu_blocks``
 (tests/decode_cases.py writes that loop out).
+
+And one-machine relaxations of partial selections (include/jss_machine.h): ``machine_reference`` and ``bottleneck_reference``, the
+NumPy mirrors of ``jss_machine_relax`` and ``jss_bottleneck_build`` and their executable definition, ``machine_library``, and
+``bottleneck_search``, biased shifting bottleneck builds defined by ``relax_machines``, ``bottleneck``, ``tabu_blocks`` and
+``evaluate_order`` (tests/machine_cases.py writes that loop out).  ``target="one_machine"`` of ``tabu_search``, ``relink_search``
+and ``brkga_search`` is ``relax_machines()`` of the empty selection, a stronger bound than ``lower_bound()`` of the reset state.
 """
 from __future__ import annotations
 
@@ -1028,8 +1034,9 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     The batch is reset and rolled out with the rule ``kind`` (``explore``: the share of random moves, so that the walkers of a
     group start from different schedules); walker w of a group walks with tenure ``lo + w % (hi - lo + 1)`` for
     ``tenure=(lo, hi)`` (an int: that tenure for all) for at most ``iters`` moves.  ``target="lower_bound"`` stops a walker
-    that reaches ``env.lower_bound()`` of the reset state -- a proof of optimality; ``None`` gives no target, an int or one
-    int per instance that target.  The result is defined by those public calls alone: ``reset``, ``lower_bound``, ``rollout``,
+    that reaches ``env.lower_bound()`` of the reset state -- a proof of optimality; ``"one_machine"`` takes
+    ``env.relax_machines()[0]`` instead, the stronger one-machine bound of the empty selection (include/jss_machine.h); ``None``
+    gives no target, an int or one int per instance that target.  The result is defined by those public calls alone: ``reset``, ``lower_bound``, ``rollout``,
     one ``tabu``, one ``evaluate_order``.
 
     ``moves="block"`` walks over block insertions instead (``BatchedJssEnv.tabu_blocks``, include/jss_block.h: candidates scored
@@ -1063,9 +1070,9 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target != "lower_bound":
-            raise ValueError("tabu_search: target is 'lower_bound', None, an int or one int per instance")
-        tgt = env.lower_bound()
+        if target not in ("lower_bound", "one_machine"):
+            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
+        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]
     elif target is None:
         tgt = None
     else:
@@ -1149,9 +1156,9 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target != "lower_bound":
-            raise ValueError("relink_search: target is 'lower_bound', None, an int or one int per instance")
-        tgt = env.lower_bound()
+        if target not in ("lower_bound", "one_machine"):
+            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
+        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]
     elif target is None:
         tgt = None
     else:
@@ -1350,8 +1357,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     one instance or on a list of them: one group of ``population`` individuals per instance and ONE batch of one env per
     instance, which is only read (``parents = repeat(arange(G), P)``).  Defined by public calls alone:
 
-    start   the batch, ``reset``, the target (``"lower_bound"``: ``env.lower_bound()`` of the reset state; None; an int or one
-            per instance); population 0 is ``evolve_keys((G * P, jmax, mmax), None, P, 0, P, generation=0, seed=seed)``, the
+    start   the batch, ``reset``, the target (``"lower_bound"``: ``env.lower_bound()`` of the reset state; ``"one_machine"``:
+            ``env.relax_machines()[0]``, the one-machine bound of the empty selection; None; an int or one per instance); population 0 is ``evolve_keys((G * P, jmax, mmax), None, P, 0, P, generation=0, seed=seed)``, the
             first individuals of every group overwritten by ``dispatching.rule_keys(instance, rule)`` for ``seed_rules`` (padding 0).
     generation t = 1 ...  ``fitness = decode_keys(keys, parents, delta)`` then ``keys = evolve_keys(keys, fitness, P, n_elite,
             n_mutant, rho, generation=t, seed=seed)`` with ``n_elite = max(1, round(elite * P))`` and ``n_mutant = round(mutants *
@@ -1388,8 +1395,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     rules = tuple(seed_rules or ())
     if len(rules) > P:
         raise ValueError("brkga_search: more seed rules than individuals")
-    if isinstance(target, str) and target != "lower_bound":
-        raise ValueError("brkga_search: target is 'lower_bound', None, an int or one int per instance")
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine"):
+        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
     S = G * P
     kw = dict(device=device) if _backend is None else dict(_backend=_backend)
 
@@ -1404,7 +1411,7 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     if isinstance(target, str):
-        tgt = host(env.lower_bound()).astype(np.int32)
+        tgt = host(env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]).astype(np.int32)
     elif target is None:
         tgt = None
     else:
@@ -1458,3 +1465,273 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     return BrkgaResult(makespan=mk[winner], keys=host(keys)[winner].copy(), start=start_out, rank=rank_out,
                        history=np.stack([host(h) for h in history], axis=1).astype(np.int32), generations=t,
                        optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, env=env)
+
+
+# ---- one-machine relaxations of partial selections, the shifting bottleneck construction (include/jss_machine.h) ----------------
+def machine_library(backend):
+    """The library of ``backend`` that exports include/jss_machine.h: ``backend.machine_lib`` (HipBackend: libjss_machine_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
+    lib = getattr(backend, "machine_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.MACHINE_SYMBOLS):
+            raise RuntimeError("relax_machines: the backend's library does not export include/jss_machine.h")
+        _abi.bind_machine(lib)
+    return lib
+
+
+def _jackson_preemptive(r, p, q):
+    """the value of Jackson's preemptive schedule: always the released unfinished operation with the largest q"""
+    n = len(r)
+    rem, done, t, left, value = list(p), [False] * n, min(r), n, 0
+    while left:
+        ready = [i for i in range(n) if not done[i] and r[i] <= t]
+        later = [r[i] for i in range(n) if not done[i] and r[i] > t]
+        if not ready:
+            t = min(later)
+            continue
+        i = max(ready, key=lambda x: (q[x], -x))
+        run = min(rem[i], min(later) - t) if later else rem[i]
+        t += run
+        if run == rem[i]:
+            done[i], left, value = True, left - 1, max(value, t + q[i])
+        else:
+            rem[i] -= run
+    return value
+
+
+def _schrage(r, p, q):
+    """Schrage's schedule: (value, starts).  The operations are listed by ascending flat index, so the lowest index wins ties"""
+    n = len(r)
+    todo, t, value, starts = set(range(n)), min(r), 0, [0] * n
+    while todo:
+        ready = [i for i in todo if r[i] <= t]
+        if not ready:
+            t = min(r[i] for i in todo)
+            continue
+        i = max(ready, key=lambda x: (q[x], -x))
+        starts[i], value = t, max(value, t + p[i] + q[i])
+        t += p[i]
+        todo.discard(i)
+    return value, starts
+
+
+def machine_reference(env_const, ops, rank=None, fixed=None, parents=None, fill=-1):
+    """include/jss_machine.h's jss_machine_relax on host arrays, written from the header's definition, one candidate after the
+    other.  ``rank`` (jmax, mmax), one table for all, or (n, jmax, mmax), or None (with nothing fixed; ``ops`` must then have its
+    (tables, jmax, mmax) shape); ``fixed`` None, an int or (n,) integers, bit m set for a sequenced machine; ``parents`` (n,) or
+    None (candidate c is env c).  Returns ``(length, lower_bound, bottleneck, jps, schrage, head, tail, rank_out)``: int32 (n,)
+    three times, (n, mmax) twice, (n, jmax, mmax) three times.  The rows of refused (-1) and cyclic (-2) candidates hold ``fill``."""
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    B = const.shape[0]
+    if rank is not None:
+        rank = np.asarray(rank, dtype=np.int64)
+        jmax, mmax = rank.shape[-2:]
+    else:
+        jmax, mmax = np.asarray(ops).shape[-2:]
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    fixed_n = None if fixed is None or np.ndim(fixed) == 0 else len(fixed)
+    n = len(parents) if parents is not None else rank.shape[0] if rank is not None and rank.ndim == 3 else fixed_n if fixed_n is not None else B
+    parents = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    masks = [0] * n if fixed is None else [int(fixed) & (2 ** 64 - 1)] * n if np.ndim(fixed) == 0 else [int(x) & (2 ** 64 - 1) for x in fixed]
+    length, lower, neck = (np.full(n, fill, np.int32) for _ in range(3))
+    jps, sch = (np.full((n, mmax), fill, np.int32) for _ in range(2))
+    head, tail, rank_out = (np.full((n, jmax, mmax), fill, np.int32) for _ in range(3))
+    for c in range(n):
+        i, mask = int(parents[c]), masks[c]
+        length[c] = -1
+        if not 0 <= i < B:
+            continue
+        J, M, tab = (int(const[i, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE))
+        if not (1 <= J <= jmax and 1 <= M <= mmax and 0 <= tab < ops.shape[0]) or mask >> M:
+            continue
+        mach, dur = ((ops[tab] >> 16) & 63).tolist(), (ops[tab] & 0xFFFF).tolist()
+        row = None if rank is None else (rank[c] if rank.ndim == 3 else rank).tolist()
+        real = [(j, k) for j in range(J) for k in range(M)]
+        on = {}
+        for j, k in real:
+            on.setdefault(mach[j][k], []).append((j, k))
+        if any(row[j][k] < 0 for j, k in real if mask >> mach[j][k] & 1):
+            continue
+        # the graph: job arcs, and the arcs of the fixed machines' orders
+        succ, pred = {o: [] for o in real}, {o: [] for o in real}
+        for j, k in real:
+            if k + 1 < M:
+                succ[(j, k)].append((j, k + 1)), pred[(j, k + 1)].append((j, k))
+        for m, its in on.items():
+            if mask >> m & 1:
+                seq = sorted(its, key=lambda o: (row[o[0]][o[1]], o))
+                for u, v in zip(seq[:-1], seq[1:]):
+                    succ[u].append(v), pred[v].append(u)
+        waits = {o: len(pred[o]) for o in real}
+        topo = [o for o in real if not waits[o]]
+        for o in topo:                                                 # (grows while it is walked)
+            for v in succ[o]:
+                waits[v] -= 1
+                if not waits[v]:
+                    topo.append(v)
+        if len(topo) < len(real):
+            length[c] = -2
+            continue
+        d = lambda o: dur[o[0]][o[1]]   # noqa: E731
+        h, t = {}, {}
+        for o in topo:
+            h[o] = max([h[u] + d(u) for u in pred[o]] or [0])
+        for o in reversed(topo):
+            t[o] = max([d(v) + t[v] for v in succ[o]] or [0])
+        length[c] = max(h[o] + d(o) for o in real)
+        jps[c], sch[c], head[c], tail[c], rank_out[c] = -1, -1, -1, -1, -1
+        for j, k in real:
+            head[c, j, k], tail[c, j, k] = h[(j, k)], t[(j, k)]
+            if mask >> mach[j][k] & 1:
+                rank_out[c, j, k] = row[j][k]
+        for m in sorted(on):
+            if mask >> m & 1:
+                continue
+            its = on[m]                                                # (ascending by flat index)
+            r, p, q = [h[o] for o in its], [d(o) for o in its], [t[o] for o in its]
+            jps[c, m] = _jackson_preemptive(r, p, q)
+            sch[c, m], starts = _schrage(r, p, q)
+            for (j, k), s in zip(its, starts):
+                rank_out[c, j, k] = s
+        free = [(int(jps[c, m]), -m) for m in on if not mask >> m & 1]
+        lower[c] = max([int(length[c])] + [v for v, _ in free])
+        neck[c] = -max(free)[1] if free else -1
+    return length, lower, neck, jps, sch, head, tail, rank_out
+
+
+def bottleneck_reference(env_const, ops, parents=None, bias=None, reopt=1, rank=None, fixed=None, fill=-1):
+    """include/jss_machine.h's jss_bottleneck_build on host arrays: the header's loop over ``machine_reference``, one candidate
+    after the other.  ``ops`` (tables, jmax, mmax); ``bias`` (n, mmax) or None; ``rank`` (n, jmax, mmax) with ``fixed`` (n,), or
+    neither.  Returns ``(makespan, rank, info, order)``: int32 (n,), (n, jmax, mmax), (n, 4), (n, mmax); the rows of refused (-1)
+    and cyclic (-2) candidates hold ``fill``."""
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64)
+    jmax, mmax = ops.shape[-2:]
+    ops = ops.reshape(-1, jmax, mmax)
+    n = len(parents) if parents is not None else const.shape[0]
+    parents = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    makespan = np.full(n, fill, np.int32)
+    rank_o, info, order = np.full((n, jmax, mmax), fill, np.int32), np.full((n, _abi.BOTTLENECK_NI), fill, np.int32), np.full((n, mmax), fill, np.int32)
+    for c in range(n):
+        par = parents[c:c + 1]
+        row = np.zeros((1, jmax, mmax), np.int64) if rank is None else np.asarray(rank, dtype=np.int64)[c:c + 1].copy()
+        mask = 0 if fixed is None else int(fixed[c]) & (2 ** 64 - 1)
+        relax = lambda r, f: machine_reference(const, ops, r, [f], par)   # noqa: E731
+        i = int(par[0])
+        tab = int(const[i, _abi.C_TABLE]) if 0 <= i < const.shape[0] else 0
+        mach = (ops[tab] >> 16) & 63 if 0 <= tab < ops.shape[0] else None
+        res = relax(row, mask)
+        first, fixed_here, tried, shorter, seq = int(res[1][0]), 0, 0, 0, []
+        while res[0][0] >= 0 and res[2][0] >= 0:
+            free = [m for m in range(mmax) if res[3][0, m] >= 0]
+            star = max(free, key=lambda m: (int(res[3][0, m]) + (0 if bias is None else int(bias[c][m])), -m))
+            row = np.where(mach == star, res[7], row)                 # its Schrage starts as ranks
+            mask |= 1 << star
+            fixed_here, seq = fixed_here + 1, seq + [star]
+            cur = int(relax(row, mask)[0][0])
+            if cur < 0:
+                res = (np.array([cur]),)
+                break
+            for _ in range(int(reopt)):
+                for k in range(mmax):
+                    if not mask >> k & 1 or k == star:
+                        continue
+                    loose = relax(row, mask & ~(1 << k))
+                    trial = np.where(mach == k, loose[7], row)
+                    new = int(relax(trial, mask)[0][0])
+                    tried += 1
+                    if 0 <= new <= cur:
+                        shorter += new < cur
+                        row, cur = trial, new
+            res = relax(row, mask)
+        makespan[c] = res[0][0]
+        if makespan[c] < 0:
+            continue
+        J, M = (int(const[i, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES))
+        rank_o[c] = -1
+        rank_o[c, :J, :M] = row[0, :J, :M]
+        info[c] = (fixed_here, tried, shorter, first)
+        order[c] = (seq + [-1] * mmax)[:mmax]
+    return makespan, rank_o, info, order
+
+
+@dataclass
+class BottleneckResult(TabuResult):
+    """What ``bottleneck_search`` returns: ``TabuResult``'s fields -- ``best_makespan`` (S,) every walker's makespan, ``info``
+    (S, 4) its build's counters, ``target`` (G,) -- and ``lower_bound`` (G,), the one-machine bound of the empty selection."""
+    lower_bound: Optional[np.ndarray] = None
+
+
+def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenure=8, seed=0, target="one_machine", device=None,
+                      _backend=None):
+    """Shifting bottleneck builds on one instance or on a list of them: ``walkers`` builds per instance, all in ONE launch
+    (``BatchedJssEnv.bottleneck``, include/jss_machine.h), on a batch of one env per instance, which is only read.  Defined by
+    public calls alone:
+
+    start   the batch, ``reset``; ``lower_bound = relax_machines()[0]``, the one-machine bound of the empty selection; the target
+            (``"one_machine"``: that bound; ``"lower_bound"``: ``env.lower_bound()``; None; an int or one per instance).
+    builds  ``bias = numpy.random.default_rng(seed).integers(0, spread + 1, (G * walkers, mmax))``, the rows of walker 0 of every
+            instance set to 0 (the unbiased build); ``bottleneck(repeat(arange(G), walkers), bias, reopt)``.
+    polish  ``polish > 0``: every build is the rank of one walker of ``tabu_blocks(rank, iters=polish, tenure=tenure)`` on a batch
+            of G * walkers envs, whose best never exceeds its start.
+    end     the lowest ``(makespan, walker)`` of every instance, its order re-timed by ``evaluate_order``.
+
+    Returns a ``BottleneckResult``; ``optimal``: the makespan reached the target."""
+    W, reopt, spread, polish = int(walkers), int(reopt), int(spread), int(polish)
+    if W < 1:
+        raise ValueError("bottleneck_search: walkers must be >= 1")
+    if not 0 <= reopt <= _abi.BOTTLENECK_MAX_REOPT:
+        raise ValueError(f"bottleneck_search: reopt must lie in [0, {_abi.BOTTLENECK_MAX_REOPT}]")
+    if not 0 <= spread < 2 ** 30 or polish < 0:
+        raise ValueError("bottleneck_search: spread in [0, 2**30), polish >= 0")
+    if not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
+        raise ValueError(f"bottleneck_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}]")
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine"):
+        raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', None, an int or one int per instance")
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError("bottleneck_search takes instances (a name, a path, an Instance, or a list of them): call "
+                                  "bottleneck on a BatchedJssEnv for anything else")
+    one = isinstance(instances, (str, os.PathLike, Instance))
+    names = [instances] if one else list(instances)
+    G = len(names)
+    if G < 1:
+        raise ValueError("bottleneck_search: need at least one instance")
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+
+    def batch(per_group):
+        if G == 1:
+            return BatchedJssEnv(names[0], batch=per_group, seed=int(seed or 0), **kw)
+        return BatchedJssEnv(names, batch=G * per_group, table_of_env=np.repeat(np.arange(G), per_group), order="interleaved",
+                             seed=int(seed or 0), **kw)
+
+    env = batch(1)
+    be = env.backend
+    env.reset()
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    bound = host(env.relax_machines()[0]).astype(np.int32)
+    if isinstance(target, str):
+        tgt = bound.copy() if target == "one_machine" else host(env.lower_bound()).astype(np.int32)
+    elif target is None:
+        tgt = None
+    else:
+        tgt = np.broadcast_to(np.asarray(target, np.int32), (G,)).copy()
+    parents = np.repeat(np.arange(G), W).astype(np.int32)
+    bias = np.random.default_rng(int(seed or 0)).integers(0, spread + 1, (G * W, env.mmax)).astype(np.int32)
+    bias[::W] = 0
+    best, rank, info = env.bottleneck(parents, bias, reopt)
+    info = host(info).astype(np.int32)
+    if polish:
+        crowd = batch(W)
+        crowd.reset()
+        best, rank, _ = crowd.tabu_blocks(rank, polish, int(tenure))
+    mk = host(best).astype(np.int32)
+    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
+    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
+    winner = (np.arange(G) * W + walker).astype(np.int32)
+    best_rank = host(rank)[winner].copy()
+    again, start = env.evaluate_order(best_rank, np.arange(G, dtype=np.int32), start=True)
+    assert np.array_equal(host(again), mk[winner])
+    return BottleneckResult(makespan=mk[winner], walker=walker, rank=best_rank, start=host(start).copy(),
+                            optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, best_makespan=mk, info=info, target=tgt,
+                            env=env, lower_bound=bound)

@@ -128,6 +128,14 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
                                   "(search.brkga_search takes a list of instances)")
 
+    def relax_machines(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not relax partial selections: call relax_machines on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
+    def bottleneck(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
