@@ -143,6 +143,15 @@ MACHINE_SYMBOLS = ("jss_machine_relax", "jss_bottleneck_build")
 BOTTLENECK_NI = 4                 # info row: machines fixed, re-sequencings tried, re-sequencings that shortened, first bound
 BOTTLENECK_MAX_REOPT = 8
 
+# include/jss_carlier.h: the companion header of Carlier's one-machine search and of the shifting bottleneck construction that
+# sequences its machines with it (its own version).  The HIP library exports both from a tenth library, libjss_carlier_hip.so;
+# the twin from libjss_cpu.so.
+CARLIER_VERSION = 1
+CARLIER_SYMBOLS = ("jss_machine_solve", "jss_bottleneck_exact")
+CARLIER_MAX_NODES = 4096
+CARLIER_MAX_DEPTH = 64
+EXACT_NI = 8                      # info row: BOTTLENECK_NI's, then nodes in total, most nodes of one problem, problems left open, sequences replaced by Schrage's
+
 _p = C.c_void_p
 
 
@@ -256,6 +265,17 @@ class JssMachineRelax(C.Structure):  # include/jss_machine.h
 class JssBottleneck(C.Structure):    # include/jss_machine.h
     _fields_ = [("n", C.c_int32), ("reopt", C.c_int32), ("parents", _p), ("rank_in", _p), ("fixed_in", _p), ("bias", _p),
                 ("makespan", _p), ("rank", _p), ("info", _p), ("order", _p)]
+
+
+class JssMachineSolve(C.Structure):  # include/jss_carlier.h
+    _fields_ = [("n", C.c_int32), ("stride", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32), ("parents", _p), ("rank", _p),
+                ("fixed", _p), ("length", _p), ("lower_bound", _p), ("bottleneck", _p), ("opt", _p), ("low", _p), ("nodes_used", _p),
+                ("proved", _p), ("head", _p), ("tail", _p), ("rank_out", _p)]
+
+
+class JssBottleneckExact(C.Structure):   # include/jss_carlier.h
+    _fields_ = [("n", C.c_int32), ("reopt", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32), ("parents", _p), ("rank_in", _p),
+                ("fixed_in", _p), ("bias", _p), ("makespan", _p), ("rank", _p), ("info", _p), ("order", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -440,6 +460,18 @@ def bind_machine(lib):
     lib.jss_machine_relax.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssMachineRelax), _p]
     lib.jss_bottleneck_build.restype = C.c_int
     lib.jss_bottleneck_build.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBottleneck), _p]
+    return lib
+
+
+def bind_carlier(lib):
+    """Attach the prototypes of include/jss_carlier.h; raises AttributeError naming the first missing symbol."""
+    for name in CARLIER_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_machine_solve.restype = C.c_int
+    lib.jss_machine_solve.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssMachineSolve), _p]
+    lib.jss_bottleneck_exact.restype = C.c_int
+    lib.jss_bottleneck_exact.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBottleneckExact), _p]
     return lib
 
 

@@ -53,6 +53,7 @@ class HipBackend:
         self._relink_lib = None
         self._decode_lib = None
         self._machine_lib = None
+        self._carlier_lib = None
 
     @property
     def beam_lib(self):
@@ -133,6 +134,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_machine_extension)")
             self._machine_lib = _abi.bind_machine(C.CDLL(path))
         return self._machine_lib
+
+    @property
+    def carlier_lib(self):
+        """libjss_carlier_hip.so (include/jss_carlier.h), loaded on first use; a missing library is an error."""
+        if self._carlier_lib is None:
+            path = _abi.library_path("libjss_carlier_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_carlier_extension)")
+            self._carlier_lib = _abi.bind_carlier(C.CDLL(path))
+        return self._carlier_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -361,6 +372,11 @@ class CpuBackend:
     def machine_lib(self):
         """the library that exports include/jss_machine.h: the twin itself"""
         return _abi.bind_machine(self.lib)
+
+    @property
+    def carlier_lib(self):
+        """the library that exports include/jss_carlier.h: the twin itself"""
+        return _abi.bind_carlier(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

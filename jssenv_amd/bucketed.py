@@ -246,6 +246,14 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
                                   "(search.bottleneck_search takes a list of instances)")
 
+    def solve_machines(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not solve one-machine problems: call solve_machines on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
+    def bottleneck_exact(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

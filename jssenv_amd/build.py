@@ -11,6 +11,8 @@
   an eighth HIP library built the same way;
 * ``libjss_machine_hip.so`` -- the one-machine relaxation and shifting bottleneck kernels (include/jss_machine.h), a ninth HIP
   library built the same way;
+* ``libjss_carlier_hip.so`` -- Carlier's one-machine search and the exact shifting bottleneck kernels (include/jss_carlier.h), a
+  tenth HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -56,9 +58,12 @@ DECODE_OUT = os.path.join(_HERE, "libjss_decode_hip.so")
 _MACHINE = os.path.join(_ROOT, "include", "jss_machine.h")   # ... and one-machine relaxations, the shifting bottleneck construction
 MACHINE_SRC = os.path.join(_HERE, "csrc", "jss_machine.hip") # (libjss_machine_hip.so: a library of its own as well)
 MACHINE_OUT = os.path.join(_HERE, "libjss_machine_hip.so")
+_CARLIER = os.path.join(_ROOT, "include", "jss_carlier.h")   # ... and Carlier's one-machine search, exact shifting bottleneck builds
+CARLIER_SRC = os.path.join(_HERE, "csrc", "jss_carlier.hip") # (libjss_carlier_hip.so: a library of its own as well)
+CARLIER_OUT = os.path.join(_HERE, "libjss_carlier_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
                 os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC),
-                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC))   # sources that libjss_hip.so does not include
+                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC), os.path.basename(CARLIER_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -76,7 +81,7 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
@@ -86,6 +91,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
         build_relink_extension(force)
         build_decode_extension(force)
         build_machine_extension(force)
+        build_carlier_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -93,7 +99,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -102,7 +108,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -111,7 +117,7 @@ def build_bound_extension(force: bool = False) -> str:
 
 
 def build_order_extension(force: bool = False) -> str:
-    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return ORDER_OUT
     tmp = ORDER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
@@ -120,7 +126,7 @@ def build_order_extension(force: bool = False) -> str:
 
 
 def build_tabu_extension(force: bool = False) -> str:
-    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return TABU_OUT
     tmp = TABU_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, TABU_SRC, "-o", tmp])
@@ -129,7 +135,7 @@ def build_tabu_extension(force: bool = False) -> str:
 
 
 def build_block_extension(force: bool = False) -> str:
-    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return BLOCK_OUT
     tmp = BLOCK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BLOCK_SRC, "-o", tmp])
@@ -138,7 +144,7 @@ def build_block_extension(force: bool = False) -> str:
 
 
 def build_relink_extension(force: bool = False) -> str:
-    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return RELINK_OUT
     tmp = RELINK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, RELINK_SRC, "-o", tmp])
@@ -147,7 +153,7 @@ def build_relink_extension(force: bool = False) -> str:
 
 
 def build_decode_extension(force: bool = False) -> str:
-    if not force and _fresh(DECODE_OUT, [DECODE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(DECODE_OUT, [DECODE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return DECODE_OUT
     tmp = DECODE_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, DECODE_SRC, "-o", tmp])
@@ -156,7 +162,7 @@ def build_decode_extension(force: bool = False) -> str:
 
 
 def build_machine_extension(force: bool = False) -> str:
-    if not force and _fresh(MACHINE_OUT, [MACHINE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(MACHINE_OUT, [MACHINE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return MACHINE_OUT
     tmp = MACHINE_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, MACHINE_SRC, "-o", tmp])
@@ -164,8 +170,17 @@ def build_machine_extension(force: bool = False) -> str:
     return MACHINE_OUT
 
 
+def build_carlier_extension(force: bool = False) -> str:
+    if not force and _fresh(CARLIER_OUT, [CARLIER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+        return CARLIER_OUT
+    tmp = CARLIER_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, CARLIER_SRC, "-o", tmp])
+    os.replace(tmp, CARLIER_OUT)
+    return CARLIER_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -21,6 +21,7 @@
 #include "jss_relink.h"
 #include "jss_decode.h"
 #include "jss_machine.h"
+#include "jss_carlier.h"
 
 namespace jss_abi {
 
@@ -489,6 +490,37 @@ inline int bottleneck_check(const JssDesc *d, const JssState *s, const JssBottle
     if (b->n < 0 || (!b->parents && b->n != d->batch)) return JSS_E_SHAPE;
     if (b->reopt < 0 || b->reopt > JSS_BOTTLENECK_MAX_REOPT) return JSS_E_SHAPE;
     return machine_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// ---- Carlier's one-machine search, shifting bottleneck constructions sequenced by it (include/jss_carlier.h) --------------------
+// What libjss_carlier_hip.so keeps in LDS for one candidate: what machine_lds_bytes counts, a row of best starts (int32) and the
+// undo stack of JSS_CARLIER_MAX_DEPTH entries of three words.
+inline long long carlier_lds_bytes(int jmax, int mmax) {
+    return 28 * order_entries8(jmax, mmax) + 4 * 64 * 4 + 3 * JSS_CARLIER_MAX_DEPTH * 4;
+}
+
+// jss_machine_solve (libjss_carlier_hip.so and the twin): the batch as jss_order_eval checks it
+inline int machine_solve_check(const JssDesc *d, const JssState *s, const JssMachineSolve *r) {
+    if (!d || !s || !r) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!r->length || (!r->rank && r->fixed) || (r->rank_out && r->rank_out == r->rank)) return JSS_E_NULL;
+    if (r->n < 0 || (!r->parents && r->n != d->batch)) return JSS_E_SHAPE;
+    if (r->nodes < 1 || r->nodes > JSS_CARLIER_MAX_NODES) return JSS_E_SHAPE;
+    if (r->stride != 0 && r->stride != d->jmax * d->mmax) return JSS_E_SHAPE;
+    return carlier_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// jss_bottleneck_exact (libjss_carlier_hip.so and the twin)
+inline int bottleneck_exact_check(const JssDesc *d, const JssState *s, const JssBottleneckExact *b) {
+    if (!d || !s || !b) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!b->makespan || !b->rank || !b->rank_in != !b->fixed_in || b->rank == b->rank_in) return JSS_E_NULL;
+    if (b->n < 0 || (!b->parents && b->n != d->batch)) return JSS_E_SHAPE;
+    if (b->reopt < 0 || b->reopt > JSS_BOTTLENECK_MAX_REOPT) return JSS_E_SHAPE;
+    if (b->nodes < 1 || b->nodes > JSS_CARLIER_MAX_NODES) return JSS_E_SHAPE;
+    return carlier_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

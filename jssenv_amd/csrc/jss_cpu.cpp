@@ -2400,3 +2400,202 @@ int jss_bottleneck_build(const JssDesc *desc, const JssState *state, const JssBo
 }
 
 }  // extern "C"
+
+// ---- Carlier's one-machine search, shifting bottleneck constructions sequenced by it (include/jss_carlier.h) -------------------
+namespace {
+
+// The header's search on machine m of a relaxed MachineProblem, whose head[] and tail[] of m's operations are the working r and q:
+// raised on the way down, restored on the way up.
+struct CarlierSearch {
+    MachineProblem &w;
+    const std::vector<int> &its;
+    const int m, budget;
+    int best = INT32_MAX, count = 0, root_jackson = 0;
+    bool open = false;
+    std::vector<int32_t> best_start;             // by index into its
+
+    CarlierSearch(MachineProblem &problem, int machine, int nodes) : w(problem), its(problem.on[machine]), m(machine), budget(nodes) {
+        root_jackson = w.jackson(m);
+        node(1);
+    }
+    int low() const { return open ? root_jackson : best; }
+    void starts_to(int32_t *rank) const {
+        for (size_t i = 0; i < its.size(); ++i) rank[its[i]] = best_start[i];
+    }
+
+    void node(int depth) {
+        ++count;
+        const int n = (int)its.size();
+        std::vector<int> ord, s((size_t)n, 0);
+        std::vector<char> done((size_t)n, 0);
+        int t = INT32_MAX, value = 0;
+        for (int i = 0; i < n; ++i) t = std::min(t, w.head[its[i]]);
+        while ((int)ord.size() < n) {
+            int pick = -1, later = INT32_MAX;
+            for (int i = 0; i < n; ++i) {
+                if (done[i]) continue;
+                if (w.head[its[i]] > t) later = std::min(later, w.head[its[i]]);
+                else if (pick < 0 || w.tail[its[i]] > w.tail[its[pick]]) pick = i;
+            }
+            if (pick < 0) {
+                t = later;
+                continue;
+            }
+            s[pick] = t, done[pick] = 1, ord.push_back(pick);
+            value = std::max(value, t + w.dur(its[pick]) + w.tail[its[pick]]);
+            t += w.dur(its[pick]);
+        }
+        if (value < best) best = value, best_start.assign(s.begin(), s.end());
+        auto r = [&](int pos) -> int32_t & { return w.head[its[ord[pos]]]; };
+        auto q = [&](int pos) -> int32_t & { return w.tail[its[ord[pos]]]; };
+        auto p = [&](int pos) { return w.dur(its[ord[pos]]); };
+        int b = 0;
+        while (s[ord[b]] + p(b) + q(b) != value) ++b;
+        int a = b;
+        while (a > 0 && s[ord[a]] == s[ord[a - 1]] + p(a - 1)) --a;
+        int c = -1;
+        for (int pos = a; pos < b; ++pos)
+            if (q(pos) < q(b)) c = pos;
+        if (c < 0) return;
+        int rJ = INT32_MAX, qJ = INT32_MAX, pJ = 0;
+        for (int pos = c + 1; pos <= b; ++pos) rJ = std::min(rJ, (int)r(pos)), qJ = std::min(qJ, (int)q(pos)), pJ += p(pos);
+        if (std::max(rJ + pJ + qJ, std::min(rJ, (int)r(c)) + pJ + p(c) + std::min(qJ, (int)q(c))) >= best) return;
+        if (count >= budget || depth >= JSS_CARLIER_MAX_DEPTH) return void(open = true);
+        for (int child = 0; child < 2; ++child) {
+            if (open) return;
+            int32_t &slot = child == 0 ? q(c) : r(c);
+            const int32_t old = slot;
+            slot = std::max((int)old, child == 0 ? pJ + qJ : rJ + pJ);
+            if (w.jackson(m) < best) {
+                if (count + 1 > budget) open = true;
+                else node(depth + 1);
+            }
+            slot = old;
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int jss_machine_solve(const JssDesc *desc, const JssState *state, const JssMachineSolve *solve, void *) {
+    if (const int rc = machine_solve_check(desc, state, solve)) return rc;
+    const JssDesc d = *desc;
+    const JssMachineSolve t = *solve;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int c) {
+        const uint64_t fixed = t.fixed ? t.fixed[c] : 0;
+        const int32_t *rank = t.rank ? t.rank + (size_t)c * t.stride : nullptr;
+        MachineProblem w;
+        if (!w.open(d, state, t.parents ? t.parents[c] : c, fixed) || w.negative_rank(rank, fixed)) return void(t.length[c] = -1);
+        const int length = w.relax(rank, fixed);
+        t.length[c] = length;
+        if (length < 0) return;
+        std::vector<int32_t> row((size_t)region, 0);
+        if (rank) std::copy(rank, rank + region, row.begin());
+        int best = -1, neck = -1;
+        uint64_t proved = 0;
+        for (int m = 0; m < mmax; ++m) {
+            int opt = -1, low = -1, used = -1;
+            if (!(fixed >> m & 1) && !w.on[m].empty()) {
+                const CarlierSearch search(w, m, t.nodes);
+                opt = search.best, low = search.low(), used = search.count;
+                proved |= (uint64_t)!search.open << m;
+                search.starts_to(row.data());
+            }
+            if (t.opt) t.opt[(size_t)c * mmax + m] = opt;
+            if (t.low) t.low[(size_t)c * mmax + m] = low;
+            if (t.nodes_used) t.nodes_used[(size_t)c * mmax + m] = used;
+            if (low > best) best = low, neck = m;
+        }
+        if (t.lower_bound) t.lower_bound[c] = std::max(length, best);
+        if (t.bottleneck) t.bottleneck[c] = neck;
+        if (t.proved) t.proved[c] = proved;
+        if (t.head) w.write_row(t.head + (size_t)c * region, d.jmax, w.head.data());
+        if (t.tail) w.write_row(t.tail + (size_t)c * region, d.jmax, w.tail.data());
+        if (t.rank_out) w.write_row(t.rank_out + (size_t)c * region, d.jmax, row.data());
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+int jss_bottleneck_exact(const JssDesc *desc, const JssState *state, const JssBottleneckExact *build, void *) {
+    if (const int rc = bottleneck_exact_check(desc, state, build)) return rc;
+    const JssDesc d = *desc;
+    const JssBottleneckExact t = *build;
+    const int region = d.jmax * d.mmax, mmax = d.mmax;
+    auto one = [&](int c) {
+        uint64_t fixed = t.fixed_in ? t.fixed_in[c] : 0;
+        std::vector<int32_t> rank((size_t)region, 0), saved;
+        if (t.rank_in) std::copy(t.rank_in + (size_t)c * region, t.rank_in + (size_t)(c + 1) * region, rank.begin());
+        MachineProblem w;
+        if (!w.open(d, state, t.parents ? t.parents[c] : c, fixed) || w.negative_rank(rank.data(), fixed)) return void(t.makespan[c] = -1);
+        const uint64_t used = w.used();
+        int length = w.relax(rank.data(), fixed);
+        int first = length, n_fixed = 0, tried = 0, shorter = 0, order[JSS_MAX_MACHINES];
+        int total = 0, most = 0, left_open = 0, replaced = 0;
+        bool at_start = true;
+        // machine k, free in the relaxation w holds, sequenced by the search's best schedule, or by Schrage's where that is
+        // cyclic: the length of (rank, with)
+        auto sequence = [&](int k, uint64_t with) {
+            {
+                const CarlierSearch search(w, k, t.nodes);
+                total += search.count, most = std::max(most, search.count), left_open += search.open;
+                search.starts_to(rank.data());
+            }
+            int len = w.relax(rank.data(), with);
+            if (len == -2) {                                            // (a cyclic relax leaves the heads and tails alone)
+                ++replaced;
+                w.schrage(k, rank.data());
+                len = w.relax(rank.data(), with);
+            }
+            return len;
+        };
+        while (length >= 0 && (used & ~fixed)) {
+            int star = -1;
+            long long high = 0;
+            for (int m = 0; m < mmax; ++m) {
+                if (!(used & ~fixed & (1ull << m))) continue;
+                const int jps = w.jackson(m);
+                if (at_start) first = std::max(first, t.info ? CarlierSearch(w, m, t.nodes).low() : jps);
+                const long long v = (long long)jps + (t.bias ? t.bias[(size_t)c * mmax + m] : 0);
+                if (star < 0 || v > high) star = m, high = v;
+            }
+            at_start = false;
+            fixed |= 1ull << star, order[n_fixed++] = star;
+            int cur = length = sequence(star, fixed);
+            if (cur < 0) break;
+            for (int round = 0; round < t.reopt; ++round)
+                for (int k = 0; k < JSS_MAX_MACHINES; ++k) {
+                    if (!(fixed >> k & 1) || k == star) continue;
+                    ++tried;                                            // (a fixed machine without operations: nothing changes)
+                    if (w.on[k].empty()) continue;
+                    w.relax(rank.data(), fixed & ~(1ull << k));
+                    saved.clear();
+                    for (int x : w.on[k]) saved.push_back(rank[x]);
+                    const int now = sequence(k, fixed);
+                    if (now >= 0 && now <= cur) {
+                        shorter += now < cur, cur = now;
+                    } else {
+                        for (size_t i = 0; i < saved.size(); ++i) rank[w.on[k][i]] = saved[i];
+                    }
+                }
+            length = w.relax(rank.data(), fixed);
+        }
+        t.makespan[c] = length;
+        if (length < 0) return;
+        w.write_row(t.rank + (size_t)c * region, d.jmax, rank.data());
+        if (t.info) {
+            int32_t *row = t.info + (size_t)c * JSS_EXACT_NI;
+            row[0] = n_fixed, row[1] = tried, row[2] = shorter, row[3] = first;
+            row[4] = total, row[5] = most, row[6] = left_open, row[7] = replaced;
+        }
+        if (t.order)
+            for (int m = 0; m < mmax; ++m) t.order[(size_t)c * mmax + m] = m < n_fixed ? order[m] : -1;
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+}  // extern "C"

@@ -1381,6 +1381,115 @@ class BatchedJssEnv:
             self._machine_keep = [r, par, fx, bs]              # alive until the launch has read them
         return (mk, out, info, fixed_order) if order else (mk, out, info)
 
+    # -- Carlier's one-machine search, shifting bottleneck constructions sequenced by it (include/jss_carlier.h) ----------------
+    def solve_machines(self, rank=None, fixed=0, parents=None, nodes: int = 256, opt: bool = False, low: bool = False,
+                       nodes_used: bool = False, proved: bool = False, head: bool = False, tail: bool = False, rank_out: bool = False):
+        """``relax_machines`` with every free machine's one-machine problem solved by Carlier's branch and bound within ``nodes``
+        search nodes per machine (in [1, 4096]), one candidate per wavefront in one launch (``jss_machine_solve``,
+        include/jss_carlier.h defines the search; integers, the same bits on every backend).  ``rank``, ``fixed`` and ``parents``
+        are ``relax_machines``'s.
+
+        Returns ``(lower_bound, length, bottleneck)``, each (n,) int32: ``length`` as there (-1 refused, -2 cyclic),
+        ``lower_bound`` the larger of it and the free machines' ``low``, ``bottleneck`` the free machine with the largest ``low``.
+        Then, each where asked for and in this order: ``opt`` (the best schedule's value, the optimum where proved), ``low`` (opt
+        where proved, else Jackson's preemptive bound) and ``nodes_used`` (n, mmax), -1 for fixed and unused machines; ``proved``
+        (n,) int64, bit m set where machine m's search ended within the budget; ``head`` and ``tail`` (n, jmax, mmax);
+        ``rank_out`` (n, jmax, mmax): ``rank`` with the free machines' operations at the starts of their best schedule.  With
+        ``nodes=1`` the best schedule is Schrage's.  Arrays of the env's backend."""
+        from .search import carlier_library
+        be = self.backend
+        lib = carlier_library(be)
+        if not 1 <= int(nodes) <= _abi.CARLIER_MAX_NODES:
+            raise ValueError(f"solve_machines: nodes must lie in [1, {_abi.CARLIER_MAX_NODES}]")
+        region = self.jmax * self.mmax
+        with be.on_device():
+            r, shape = None, None
+            if rank is not None:
+                r = be.as_device(rank, "int32")
+                shape = tuple(r.shape)
+                if not (shape == (self.jmax, self.mmax) or (len(shape) == 3 and shape[1:] == (self.jmax, self.mmax))):
+                    raise ValueError(f"solve_machines: rank must have shape {(self.jmax, self.mmax)} or (n, {self.jmax}, {self.mmax}), got {shape}")
+            par, n = self._machine_call_start("solve_machines", parents, shape[0] if shape and len(shape) == 3 else None, fixed)
+            if shape and len(shape) == 3 and shape[0] != n:
+                raise ValueError(f"solve_machines: {shape[0]} rank tables for {n} candidates")
+            masks = self._fixed_masks(fixed, n, "solve_machines")
+            if r is None and masks.any():
+                raise ValueError("solve_machines: a fixed machine needs a rank")
+            fx = be.from_numpy(masks.view(np.int64)) if masks.any() else None
+
+            def out(*shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            length, lower, neck = out(n), out(n), out(n)
+            rows = [out(n, self.mmax) if want else None for want in (opt, low, nodes_used)] + [be.zeros((n,), "int64") if proved else None] + \
+                   [out(n, self.jmax, self.mmax) if want else None for want in (head, tail, rank_out)]
+            if n:
+                p = be.ptr
+                arg = _abi.JssMachineSolve(n, region if shape and len(shape) == 3 else 0, int(nodes), 0, p(par), p(r), p(fx), p(length),
+                                           p(lower), p(neck), *(p(x) for x in rows))
+                rc = lib.jss_machine_solve(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_machine_solve")
+            self._machine_keep = [r, par, fx]                  # alive until the launch has read them
+        return (lower, length, neck) + tuple(x for x in rows if x is not None)
+
+    def bottleneck_exact(self, parents=None, bias=None, reopt: int = 1, nodes: int = 256, rank=None, fixed=None, order: bool = False):
+        """``bottleneck`` with every machine sequenced by the best schedule of Carlier's branch and bound (at most ``nodes`` search
+        nodes per one-machine problem, in [1, 4096]) instead of Schrage's: the shifting bottleneck procedure with exact
+        one-machine solutions, all candidates in one launch (``jss_bottleneck_exact``, include/jss_carlier.h; integers, the same
+        bits on every backend).  The arguments are ``bottleneck``'s; ``nodes=1`` builds what it builds.  ta01 unbiased: 1512 / 1345
+        / 1352 at reopt 0 / 1 / 3 where ``bottleneck`` gives 1633 / 1475 / 1402.
+
+        Returns ``(makespan, rank, info)`` as ``bottleneck`` does, ``info`` (n, 8): its four counters (the lower bound from the
+        searches' ``low``), then the nodes of all searches, the most nodes of one problem, the problems left open by the budget and
+        the sequences replaced by Schrage's because they closed a cycle; with ``order`` also the (n, mmax) machines in the order
+        they were fixed."""
+        from .search import carlier_library
+        be = self.backend
+        lib = carlier_library(be)
+        if not 0 <= int(reopt) <= _abi.BOTTLENECK_MAX_REOPT:
+            raise ValueError(f"bottleneck_exact: reopt must lie in [0, {_abi.BOTTLENECK_MAX_REOPT}]")
+        if not 1 <= int(nodes) <= _abi.CARLIER_MAX_NODES:
+            raise ValueError(f"bottleneck_exact: nodes must lie in [1, {_abi.CARLIER_MAX_NODES}]")
+        if (rank is None) != (fixed is None):
+            raise ValueError("bottleneck_exact: rank and fixed are given together")
+        with be.on_device():
+            r = None
+            if rank is not None:
+                r = be.as_device(rank, "int32")
+                if len(r.shape) != 3 or tuple(r.shape[1:]) != (self.jmax, self.mmax):
+                    raise ValueError(f"bottleneck_exact: rank must have shape (n, {self.jmax}, {self.mmax}), got {tuple(r.shape)}")
+            par, n = self._machine_call_start("bottleneck_exact", parents, int(r.shape[0]) if r is not None else None, fixed)
+            if r is not None and int(r.shape[0]) != n:
+                raise ValueError(f"bottleneck_exact: {int(r.shape[0])} rank tables for {n} candidates")
+            fx = None if fixed is None else be.from_numpy(self._fixed_masks(fixed, n, "bottleneck_exact").view(np.int64))
+            bs = None
+            if bias is not None:
+                bs = be.as_device(bias, "int32")
+                if getattr(be, "torch", None) is None:
+                    bs = bs.copy()
+                if tuple(bs.shape) != (n, self.mmax):
+                    raise ValueError(f"bottleneck_exact: bias must have shape {(n, self.mmax)}, got {tuple(bs.shape)}")
+            mk = be.zeros((n,), "int32")
+            mk -= 1
+            out = be.zeros((n, self.jmax, self.mmax), "int32")
+            out -= 1
+            info = be.zeros((n, _abi.EXACT_NI), "int32")
+            fixed_order = None
+            if order:
+                fixed_order = be.zeros((n, self.mmax), "int32")
+                fixed_order -= 1
+            if n:
+                p = be.ptr
+                arg = _abi.JssBottleneckExact(n, int(reopt), int(nodes), 0, p(par), p(r), p(fx), p(bs), p(mk), p(out), p(info), p(fixed_order))
+                rc = lib.jss_bottleneck_exact(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_bottleneck_exact")
+            self._machine_keep = [r, par, fx, bs]              # alive until the launch has read them
+        return (mk, out, info, fixed_order) if order else (mk, out, info)
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

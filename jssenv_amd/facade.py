@@ -434,6 +434,31 @@ class JssEnv(gymnasium_base("Env")):
         host = [np.asarray(b.backend.numpy(x))[0] for x in out]
         return (int(host[0]),) + tuple(host[1:])
 
+    def solve_machines(self, rank=None, fixed: int = 0, nodes: int = 256, opt: bool = False, low: bool = False, nodes_used: bool = False,
+                       proved: bool = False, head: bool = False, tail: bool = False, rank_out: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.solve_machines`` (include/jss_carlier.h): ``relax_machines`` with the free machines'
+        one-machine problems solved by Carlier's branch and bound within ``nodes`` search nodes each.  Returns ``(lower_bound,
+        length, bottleneck)``, ints, then each where asked for ``opt``, ``low``, ``nodes_used`` (mmax,), ``proved`` (an int, the
+        mask), ``head``, ``tail`` and ``rank_out`` (jmax, mmax), host arrays."""
+        b = self._b
+        out = b.solve_machines(None if rank is None else self._machine_row(rank), int(fixed), None, nodes, opt, low, nodes_used, proved,
+                               head, tail, rank_out)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        at = 3 + int(opt) + int(low) + int(nodes_used)
+        if proved:
+            host[at] = int(host[at]) & (2 ** 64 - 1)
+        return tuple(int(x) for x in host[:3]) + tuple(host[3:])
+
+    def bottleneck_exact(self, bias=None, reopt: int = 1, nodes: int = 256, rank=None, fixed=None, order: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.bottleneck_exact`` (include/jss_carlier.h): one shifting bottleneck construction with
+        the machines sequenced by Carlier's branch and bound.  Returns ``(makespan, rank, info[, order])``: an int (-1 refused, -2
+        cyclic) and host arrays, ``info`` with 8 entries."""
+        b = self._b
+        out = b.bottleneck_exact(None, None if bias is None else np.asarray(bias, np.int32).reshape(1, -1), reopt, nodes,
+                                 None if rank is None else self._machine_row(rank), None if fixed is None else int(fixed), order)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return (int(host[0]),) + tuple(host[1:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

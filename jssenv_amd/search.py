@@ -36,6 +36,10 @@ NumPy mirrors of ``jss_machine_relax`` and ``jss_bottleneck_build`` and their ex
 ``bottleneck_search``, biased shifting bottleneck builds defined by ``relax_machines``, ``bottleneck``, ``tabu_blocks`` and
 ``evaluate_order`` (tests/machine_cases.py writes that loop out).  ``target="one_machine"`` of ``tabu_search``, ``relink_search``
 and ``brkga_search`` is ``relax_machines()`` of the empty selection, a stronger bound than ``lower_bound()`` of the reset state.
+
+And Carlier's branch and bound for those one-machine problems (include/jss_carlier.h): ``carlier_reference``, the search itself,
+``solve_reference`` and ``bottleneck_exact_reference``, the NumPy mirrors of ``jss_machine_solve`` and ``jss_bottleneck_exact`` and
+their executable definition, ``carlier_library``, ``bottleneck_search(nodes=...)`` and ``target="one_machine_exact"``.
 """
 from __future__ import annotations
 
@@ -1035,7 +1039,8 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     group start from different schedules); walker w of a group walks with tenure ``lo + w % (hi - lo + 1)`` for
     ``tenure=(lo, hi)`` (an int: that tenure for all) for at most ``iters`` moves.  ``target="lower_bound"`` stops a walker
     that reaches ``env.lower_bound()`` of the reset state -- a proof of optimality; ``"one_machine"`` takes
-    ``env.relax_machines()[0]`` instead, the stronger one-machine bound of the empty selection (include/jss_machine.h); ``None``
+    ``env.relax_machines()[0]`` instead, the stronger one-machine bound of the empty selection (include/jss_machine.h), and
+    ``"one_machine_exact"`` ``env.solve_machines()[0]``, that bound with the one-machine problems solved (include/jss_carlier.h); ``None``
     gives no target, an int or one int per instance that target.  The result is defined by those public calls alone: ``reset``, ``lower_bound``, ``rollout``,
     one ``tabu``, one ``evaluate_order``.
 
@@ -1070,9 +1075,9 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine"):
-            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
-        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]
+        if target not in ("lower_bound", "one_machine", "one_machine_exact"):
+            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
+        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine" else env.solve_machines()[0]
     elif target is None:
         tgt = None
     else:
@@ -1156,9 +1161,9 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine"):
-            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
-        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]
+        if target not in ("lower_bound", "one_machine", "one_machine_exact"):
+            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
+        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine" else env.solve_machines()[0]
     elif target is None:
         tgt = None
     else:
@@ -1358,7 +1363,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     instance, which is only read (``parents = repeat(arange(G), P)``).  Defined by public calls alone:
 
     start   the batch, ``reset``, the target (``"lower_bound"``: ``env.lower_bound()`` of the reset state; ``"one_machine"``:
-            ``env.relax_machines()[0]``, the one-machine bound of the empty selection; None; an int or one per instance); population 0 is ``evolve_keys((G * P, jmax, mmax), None, P, 0, P, generation=0, seed=seed)``, the
+            ``env.relax_machines()[0]``, the one-machine bound of the empty selection; ``"one_machine_exact"``:
+            ``env.solve_machines()[0]``; None; an int or one per instance); population 0 is ``evolve_keys((G * P, jmax, mmax), None, P, 0, P, generation=0, seed=seed)``, the
             first individuals of every group overwritten by ``dispatching.rule_keys(instance, rule)`` for ``seed_rules`` (padding 0).
     generation t = 1 ...  ``fitness = decode_keys(keys, parents, delta)`` then ``keys = evolve_keys(keys, fitness, P, n_elite,
             n_mutant, rho, generation=t, seed=seed)`` with ``n_elite = max(1, round(elite * P))`` and ``n_mutant = round(mutants *
@@ -1395,8 +1401,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     rules = tuple(seed_rules or ())
     if len(rules) > P:
         raise ValueError("brkga_search: more seed rules than individuals")
-    if isinstance(target, str) and target not in ("lower_bound", "one_machine"):
-        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', None, an int or one int per instance")
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine", "one_machine_exact"):
+        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
     S = G * P
     kw = dict(device=device) if _backend is None else dict(_backend=_backend)
 
@@ -1411,7 +1417,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     if isinstance(target, str):
-        tgt = host(env.lower_bound() if target == "lower_bound" else env.relax_machines()[0]).astype(np.int32)
+        tgt = host(env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
+                   else env.solve_machines()[0]).astype(np.int32)
     elif target is None:
         tgt = None
     else:
@@ -1664,7 +1671,7 @@ class BottleneckResult(TabuResult):
 
 
 def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenure=8, seed=0, target="one_machine", device=None,
-                      _backend=None):
+                      _backend=None, nodes=0):
     """Shifting bottleneck builds on one instance or on a list of them: ``walkers`` builds per instance, all in ONE launch
     (``BatchedJssEnv.bottleneck``, include/jss_machine.h), on a batch of one env per instance, which is only read.  Defined by
     public calls alone:
@@ -1677,8 +1684,15 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
             of G * walkers envs, whose best never exceeds its start.
     end     the lowest ``(makespan, walker)`` of every instance, its order re-timed by ``evaluate_order``.
 
+    ``nodes > 0`` (at most 4096) sequences the machines exactly (include/jss_carlier.h): the builds are
+    ``bottleneck_exact(parents, bias, reopt, nodes)``, ``info`` has their 8 counters, ``lower_bound = solve_machines(nodes=nodes)[0]``,
+    and ``"one_machine_exact"`` is the target that means this bound (``"one_machine"`` means it too then).  ``nodes=0`` is the path
+    above, bit for bit.
+
     Returns a ``BottleneckResult``; ``optimal``: the makespan reached the target."""
-    W, reopt, spread, polish = int(walkers), int(reopt), int(spread), int(polish)
+    W, reopt, spread, polish, nodes = int(walkers), int(reopt), int(spread), int(polish), int(nodes)
+    if not 0 <= nodes <= _abi.CARLIER_MAX_NODES:
+        raise ValueError(f"bottleneck_search: nodes must lie in [0, {_abi.CARLIER_MAX_NODES}]")
     if W < 1:
         raise ValueError("bottleneck_search: walkers must be >= 1")
     if not 0 <= reopt <= _abi.BOTTLENECK_MAX_REOPT:
@@ -1687,8 +1701,9 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
         raise ValueError("bottleneck_search: spread in [0, 2**30), polish >= 0")
     if not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
         raise ValueError(f"bottleneck_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}]")
-    if isinstance(target, str) and target not in ("lower_bound", "one_machine"):
-        raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', None, an int or one int per instance")
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine") + (("one_machine_exact",) if nodes else ()):
+        raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', None, an int or one int per instance"
+                         " ('one_machine_exact' with nodes > 0)")
     if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
         raise NotImplementedError("bottleneck_search takes instances (a name, a path, an Instance, or a list of them): call "
                                   "bottleneck on a BatchedJssEnv for anything else")
@@ -1709,9 +1724,9 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     be = env.backend
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
-    bound = host(env.relax_machines()[0]).astype(np.int32)
+    bound = host(env.solve_machines(nodes=nodes)[0] if nodes else env.relax_machines()[0]).astype(np.int32)
     if isinstance(target, str):
-        tgt = bound.copy() if target == "one_machine" else host(env.lower_bound()).astype(np.int32)
+        tgt = bound.copy() if target != "lower_bound" else host(env.lower_bound()).astype(np.int32)
     elif target is None:
         tgt = None
     else:
@@ -1719,7 +1734,7 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     parents = np.repeat(np.arange(G), W).astype(np.int32)
     bias = np.random.default_rng(int(seed or 0)).integers(0, spread + 1, (G * W, env.mmax)).astype(np.int32)
     bias[::W] = 0
-    best, rank, info = env.bottleneck(parents, bias, reopt)
+    best, rank, info = env.bottleneck_exact(parents, bias, reopt, nodes) if nodes else env.bottleneck(parents, bias, reopt)
     info = host(info).astype(np.int32)
     if polish:
         crowd = batch(W)
@@ -1735,3 +1750,195 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     return BottleneckResult(makespan=mk[winner], walker=walker, rank=best_rank, start=host(start).copy(),
                             optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, best_makespan=mk, info=info, target=tgt,
                             env=env, lower_bound=bound)
+
+
+# ---- Carlier's one-machine search, shifting bottleneck constructions sequenced by it (include/jss_carlier.h) --------------------
+def carlier_library(backend):
+    """The library of ``backend`` that exports include/jss_carlier.h: ``backend.carlier_lib`` (HipBackend: libjss_carlier_hip.so,
+    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
+    lib = getattr(backend, "carlier_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.CARLIER_SYMBOLS):
+            raise RuntimeError("solve_machines: the backend's library does not export include/jss_carlier.h")
+        _abi.bind_carlier(lib)
+    return lib
+
+
+def carlier_reference(r, p, q, nodes):
+    """include/jss_carlier.h's one-machine search, written from the header: the operations by ascending flat index with heads
+    ``r``, durations ``p`` and tails ``q``, a budget of ``nodes``.  Returns ``(opt, proved, low, nodes_used, starts)``."""
+    r, p, q, n = list(r), list(p), list(q), len(r)
+    st = dict(best=None, starts=None, count=0, open=False)
+    root = _jackson_preemptive(r, p, q)
+
+    def node(depth):
+        # 1. counted; Schrage's schedule of the working r and q, in the order it schedules
+        st["count"] += 1
+        todo, t, value, s, order = set(range(n)), min(r), 0, [0] * n, []
+        while todo:
+            ready = [i for i in todo if r[i] <= t]
+            if not ready:
+                t = min(r[i] for i in todo)
+                continue
+            i = max(ready, key=lambda x: (q[x], -x))
+            s[i], value = t, max(value, t + p[i] + q[i])
+            t += p[i]
+            todo.discard(i)
+            order.append(i)
+        if st["best"] is None or value < st["best"]:
+            st["best"], st["starts"] = value, list(s)
+        # 2. positions in that order
+        b = min(pos for pos, i in enumerate(order) if s[i] + p[i] + q[i] == value)
+        a = b
+        while a > 0 and s[order[a]] == s[order[a - 1]] + p[order[a - 1]]:
+            a -= 1
+        critical = [pos for pos in range(a, b) if q[order[pos]] < q[order[b]]]
+        if not critical:
+            return
+        c, J = order[critical[-1]], order[critical[-1] + 1:b + 1]
+        # 3.
+        rJ, qJ, pJ = min(r[i] for i in J), min(q[i] for i in J), sum(p[i] for i in J)
+        if max(rJ + pJ + qJ, min(rJ, r[c]) + pJ + p[c] + min(qJ, q[c])) >= st["best"]:
+            return
+        # 4. the budget is spent, or the depth: no child could be entered.  Else c before J, then c after J
+        if st["count"] >= nodes or depth >= _abi.CARLIER_MAX_DEPTH:
+            st["open"] = True
+            return
+        for values, raised in ((q, pJ + qJ), (r, rJ + pJ)):
+            if st["open"]:
+                return
+            old = values[c]
+            values[c] = max(old, raised)
+            if _jackson_preemptive(r, p, q) < st["best"]:
+                if st["count"] + 1 > nodes:
+                    st["open"] = True
+                else:
+                    node(depth + 1)
+            values[c] = old
+
+    node(1)
+    proved = not st["open"]
+    return st["best"], proved, st["best"] if proved else root, st["count"], st["starts"]
+
+
+def _machine_problems(const, ops, parent, relaxed, c):
+    """the one-machine problems of candidate c of a machine_reference result: {m: (its, r, p, q)} for the free machines with
+    operations, `its` the (j, k) ascending by flat index"""
+    J, M, tab = (int(const[parent, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE))
+    mach, dur = ((ops[tab] >> 16) & 63).tolist(), (ops[tab] & 0xFFFF).tolist()
+    on = {}
+    for j in range(J):
+        for k in range(M):
+            on.setdefault(mach[j][k], []).append((j, k))
+    head, tail = relaxed[5][c], relaxed[6][c]
+    return {m: (its, [int(head[o]) for o in its], [dur[j][k] for j, k in its], [int(tail[o]) for o in its])
+            for m, its in sorted(on.items()) if relaxed[3][c, m] >= 0}
+
+
+def solve_reference(env_const, ops, rank=None, fixed=None, parents=None, nodes=256, fill=-1):
+    """include/jss_carlier.h's jss_machine_solve on host arrays, written from the header: ``machine_reference`` for what the
+    header takes from jss_machine.h, then ``carlier_reference`` on every free machine.  Returns ``(length, lower_bound,
+    bottleneck, opt, low, nodes_used, proved, head, tail, rank_out)``: int32 (n,) three times, (n, mmax) three times, uint64 (n,),
+    int32 (n, jmax, mmax) three times.  The rows of refused (-1) and cyclic (-2) candidates hold ``fill``."""
+    relaxed = machine_reference(env_const, ops, rank, fixed, parents, fill)
+    length, _, _, jps, _, head, tail, rank_out = relaxed
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    jmax, mmax = head.shape[1:]
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    n = length.size
+    parents = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    lower, neck = np.full(n, fill, np.int32), np.full(n, fill, np.int32)
+    opt, low, used = (np.full((n, mmax), fill, np.int32) for _ in range(3))
+    proved = np.full(n, np.uint64(np.int64(fill).astype(np.uint64)), np.uint64)
+    rank_out = rank_out.copy()
+    for c in range(n):
+        if length[c] < 0:
+            continue
+        opt[c], low[c], used[c], mask = -1, -1, -1, 0
+        for m, (its, r, p, q) in _machine_problems(const, ops, int(parents[c]), relaxed, c).items():
+            opt[c, m], ok, low[c, m], used[c, m], starts = carlier_reference(r, p, q, nodes)
+            mask |= int(ok) << m
+            for o, s in zip(its, starts):
+                rank_out[c][o] = s
+        free = [(int(low[c, m]), -m) for m in range(mmax) if low[c, m] >= 0 and jps[c, m] >= 0]
+        lower[c] = max([int(length[c])] + [v for v, _ in free])
+        neck[c] = -max(free)[1] if free else -1
+        proved[c] = mask
+    return length, lower, neck, opt, low, used, proved, head, tail, rank_out
+
+
+def bottleneck_exact_reference(env_const, ops, parents=None, bias=None, reopt=1, nodes=256, rank=None, fixed=None, fill=-1):
+    """include/jss_carlier.h's jss_bottleneck_exact on host arrays: ``bottleneck_reference``'s loop with the machines sequenced by
+    ``carlier_reference``'s best schedule, by Schrage's where that closes a cycle.  Returns ``(makespan, rank, info, order)``:
+    int32 (n,), (n, jmax, mmax), (n, 8), (n, mmax); the rows of refused (-1) and cyclic (-2) candidates hold ``fill``."""
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    ops = np.asarray(ops, dtype=np.int64)
+    jmax, mmax = ops.shape[-2:]
+    ops = ops.reshape(-1, jmax, mmax)
+    n = len(parents) if parents is not None else const.shape[0]
+    parents = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    makespan = np.full(n, fill, np.int32)
+    rank_o, info, order = np.full((n, jmax, mmax), fill, np.int32), np.full((n, _abi.EXACT_NI), fill, np.int32), np.full((n, mmax), fill, np.int32)
+    for c in range(n):
+        par = parents[c:c + 1]
+        row = np.zeros((1, jmax, mmax), np.int64) if rank is None else np.asarray(rank, dtype=np.int64)[c:c + 1].copy()
+        mask = 0 if fixed is None else int(fixed[c]) & (2 ** 64 - 1)
+        relax = lambda r, f: machine_reference(const, ops, r, [f], par)   # noqa: E731
+        i = int(par[0])
+        tab = int(const[i, _abi.C_TABLE]) if 0 <= i < const.shape[0] else 0
+        mach = (ops[tab] >> 16) & 63 if 0 <= tab < ops.shape[0] else None
+        count = dict(total=0, most=0, open=0, replaced=0)
+
+        def sequence(loose, k, row, with_k):
+            """machine k, free in the relaxation `loose`, sequenced: (the rank table, the length of (table, with_k))"""
+            its, r, p, q = _machine_problems(const, ops, i, loose, 0)[k]
+            _, ok, _, used, starts = carlier_reference(r, p, q, nodes)
+            count["total"] += used
+            count["most"] = max(count["most"], used)
+            count["open"] += not ok
+            trial = row.copy()
+            for o, s in zip(its, starts):
+                trial[0][o] = s
+            new = int(relax(trial, with_k)[0][0])
+            if new == -2:
+                count["replaced"] += 1
+                trial = np.where(mach == k, loose[7], row)             # its Schrage starts as ranks
+                new = int(relax(trial, with_k)[0][0])
+            return trial, new
+
+        res = relax(row, mask)
+        first, fixed_here, tried, shorter, seq = int(res[1][0]), 0, 0, 0, []
+        if res[0][0] >= 0:
+            first = max([int(res[0][0])] + [carlier_reference(r, p, q, nodes)[2] for _, r, p, q in _machine_problems(const, ops, i, res, 0).values()])
+        while res[0][0] >= 0 and res[2][0] >= 0:
+            free = [m for m in range(mmax) if res[3][0, m] >= 0]
+            star = max(free, key=lambda m: (int(res[3][0, m]) + (0 if bias is None else int(bias[c][m])), -m))
+            mask |= 1 << star
+            row, cur = sequence(res, star, row, mask)
+            fixed_here, seq = fixed_here + 1, seq + [star]
+            if cur < 0:
+                res = (np.array([cur]),)
+                break
+            for _ in range(int(reopt)):
+                for k in range(mmax):
+                    if not mask >> k & 1 or k == star:
+                        continue
+                    tried += 1
+                    loose = relax(row, mask & ~(1 << k))
+                    if loose[3][0, k] < 0:                             # (a fixed machine without operations: nothing changes)
+                        continue
+                    trial, new = sequence(loose, k, row, mask)
+                    if 0 <= new <= cur:
+                        shorter += new < cur
+                        row, cur = trial, new
+            res = relax(row, mask)
+        makespan[c] = res[0][0]
+        if makespan[c] < 0:
+            continue
+        J, M = (int(const[i, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES))
+        rank_o[c] = -1
+        rank_o[c, :J, :M] = row[0, :J, :M]
+        info[c] = (fixed_here, tried, shorter, first, count["total"], count["most"], count["open"], count["replaced"])
+        order[c] = (seq + [-1] * mmax)[:mmax]
+    return makespan, rank_o, info, order

@@ -136,6 +136,14 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
                                   "(search.bottleneck_search takes a list of instances)")
 
+    def solve_machines(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not solve one-machine problems: call solve_machines on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
+    def bottleneck_exact(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
+                                  "(search.bottleneck_search takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
