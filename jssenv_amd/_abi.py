@@ -152,6 +152,14 @@ CARLIER_MAX_NODES = 4096
 CARLIER_MAX_DEPTH = 64
 EXACT_NI = 8                      # info row: BOTTLENECK_NI's, then nodes in total, most nodes of one problem, problems left open, sequences replaced by Schrage's
 
+# include/jss_propagate.h: the companion header of constraint propagation on operation windows (its own version).  The HIP library
+# exports it from an eleventh library, libjss_propagate_hip.so; the twin from libjss_cpu.so.
+PROPAGATE_VERSION = 1
+PROPAGATE_SYMBOLS = ("jss_propagate",)
+PROPAGATE_MAX_PASSES = 4096
+PROPAGATE_MAX_TIME = 0x3FFFFFFF
+PROPAGATE_FIXPOINT, PROPAGATE_REFUTED, PROPAGATE_BUDGET = 0, 1, 2
+
 _p = C.c_void_p
 
 
@@ -276,6 +284,12 @@ class JssMachineSolve(C.Structure):  # include/jss_carlier.h
 class JssBottleneckExact(C.Structure):   # include/jss_carlier.h
     _fields_ = [("n", C.c_int32), ("reopt", C.c_int32), ("nodes", C.c_int32), ("reserved", C.c_int32), ("parents", _p), ("rank_in", _p),
                 ("fixed_in", _p), ("bias", _p), ("makespan", _p), ("rank", _p), ("info", _p), ("order", _p)]
+
+
+class JssPropagate(C.Structure):     # include/jss_propagate.h
+    _fields_ = [("n", C.c_int32), ("stride", C.c_int32), ("win_stride", C.c_int32), ("passes", C.c_int32), ("parents", _p), ("rank", _p),
+                ("fixed", _p), ("ub", _p), ("est_in", _p), ("lct_in", _p), ("hyp_op", _p), ("hyp_est", _p), ("hyp_lct", _p),
+                ("status", _p), ("passes_used", _p), ("est", _p), ("lct", _p)]
 
 
 def library_path(name: str = "libjss_hip.so") -> str:
@@ -472,6 +486,16 @@ def bind_carlier(lib):
     lib.jss_machine_solve.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssMachineSolve), _p]
     lib.jss_bottleneck_exact.restype = C.c_int
     lib.jss_bottleneck_exact.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssBottleneckExact), _p]
+    return lib
+
+
+def bind_propagate(lib):
+    """Attach the prototype of include/jss_propagate.h; raises AttributeError naming the missing symbol."""
+    for name in PROPAGATE_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    lib.jss_propagate.restype = C.c_int
+    lib.jss_propagate.argtypes = [C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssPropagate), _p]
     return lib
 
 

@@ -54,6 +54,7 @@ class HipBackend:
         self._decode_lib = None
         self._machine_lib = None
         self._carlier_lib = None
+        self._propagate_lib = None
 
     @property
     def beam_lib(self):
@@ -144,6 +145,16 @@ class HipBackend:
                 raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_carlier_extension)")
             self._carlier_lib = _abi.bind_carlier(C.CDLL(path))
         return self._carlier_lib
+
+    @property
+    def propagate_lib(self):
+        """libjss_propagate_hip.so (include/jss_propagate.h), loaded on first use; a missing library is an error."""
+        if self._propagate_lib is None:
+            path = _abi.library_path("libjss_propagate_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_propagate_extension)")
+            self._propagate_lib = _abi.bind_propagate(C.CDLL(path))
+        return self._propagate_lib
 
     # -- memory ----------------------------------------------------------------------------
     def zeros(self, shape, dtype):
@@ -377,6 +388,11 @@ class CpuBackend:
     def carlier_lib(self):
         """the library that exports include/jss_carlier.h: the twin itself"""
         return _abi.bind_carlier(self.lib)
+
+    @property
+    def propagate_lib(self):
+        """the library that exports include/jss_propagate.h: the twin itself"""
+        return _abi.bind_propagate(self.lib)
 
     def zeros(self, shape, dtype):
         return np.zeros(shape, dtype=getattr(np, dtype))

@@ -254,6 +254,10 @@ class BucketedJssEnv:
         raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
                                   "(search.bottleneck_search takes a list of instances)")
 
+    def propagate(self, *args, **kwargs):
+        raise NotImplementedError("BucketedJssEnv does not propagate operation windows: call propagate on a BatchedJssEnv "
+                                  "(search.destructive_bound takes a list of instances)")
+
     def synchronize(self):
         for _, b in self._each():
             b.synchronize()

@@ -13,6 +13,8 @@
   library built the same way;
 * ``libjss_carlier_hip.so`` -- Carlier's one-machine search and the exact shifting bottleneck kernels (include/jss_carlier.h), a
   tenth HIP library built the same way;
+* ``libjss_propagate_hip.so`` -- constraint propagation on operation windows (include/jss_propagate.h), an eleventh HIP library
+  built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -61,9 +63,12 @@ MACHINE_OUT = os.path.join(_HERE, "libjss_machine_hip.so")
 _CARLIER = os.path.join(_ROOT, "include", "jss_carlier.h")   # ... and Carlier's one-machine search, exact shifting bottleneck builds
 CARLIER_SRC = os.path.join(_HERE, "csrc", "jss_carlier.hip") # (libjss_carlier_hip.so: a library of its own as well)
 CARLIER_OUT = os.path.join(_HERE, "libjss_carlier_hip.so")
+_PROPAGATE = os.path.join(_ROOT, "include", "jss_propagate.h")   # ... and constraint propagation on operation windows (jss_propagate)
+PROPAGATE_SRC = os.path.join(_HERE, "csrc", "jss_propagate.hip") # (libjss_propagate_hip.so: a library of its own as well)
+PROPAGATE_OUT = os.path.join(_HERE, "libjss_propagate_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
                 os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC),
-                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC), os.path.basename(CARLIER_SRC))   # sources that libjss_hip.so does not include
+                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC), os.path.basename(CARLIER_SRC), os.path.basename(PROPAGATE_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -81,7 +86,7 @@ def _fresh(out, deps):
 
 def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
     csrc = os.path.dirname(SRC)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f not in _OWN_LIBRARY] + [_HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]
     if out == OUT:                     # the default output: the package's other HIP libraries go with it
         build_beam_extension(force)
         build_bound_extension(force)
@@ -92,6 +97,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
         build_decode_extension(force)
         build_machine_extension(force)
         build_carlier_extension(force)
+        build_propagate_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -99,7 +105,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
 
 
 def build_beam_extension(force: bool = False) -> str:
-    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(BEAM_OUT, [BEAM_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return BEAM_OUT
     tmp = BEAM_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BEAM_SRC, "-o", tmp])
@@ -108,7 +114,7 @@ def build_beam_extension(force: bool = False) -> str:
 
 
 def build_bound_extension(force: bool = False) -> str:
-    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(BOUND_OUT, [BOUND_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return BOUND_OUT
     tmp = BOUND_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BOUND_SRC, "-o", tmp])
@@ -117,7 +123,7 @@ def build_bound_extension(force: bool = False) -> str:
 
 
 def build_order_extension(force: bool = False) -> str:
-    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(ORDER_OUT, [ORDER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return ORDER_OUT
     tmp = ORDER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, ORDER_SRC, "-o", tmp])
@@ -126,7 +132,7 @@ def build_order_extension(force: bool = False) -> str:
 
 
 def build_tabu_extension(force: bool = False) -> str:
-    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(TABU_OUT, [TABU_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return TABU_OUT
     tmp = TABU_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, TABU_SRC, "-o", tmp])
@@ -135,7 +141,7 @@ def build_tabu_extension(force: bool = False) -> str:
 
 
 def build_block_extension(force: bool = False) -> str:
-    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(BLOCK_OUT, [BLOCK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return BLOCK_OUT
     tmp = BLOCK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, BLOCK_SRC, "-o", tmp])
@@ -144,7 +150,7 @@ def build_block_extension(force: bool = False) -> str:
 
 
 def build_relink_extension(force: bool = False) -> str:
-    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(RELINK_OUT, [RELINK_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return RELINK_OUT
     tmp = RELINK_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, RELINK_SRC, "-o", tmp])
@@ -153,7 +159,7 @@ def build_relink_extension(force: bool = False) -> str:
 
 
 def build_decode_extension(force: bool = False) -> str:
-    if not force and _fresh(DECODE_OUT, [DECODE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(DECODE_OUT, [DECODE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return DECODE_OUT
     tmp = DECODE_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, DECODE_SRC, "-o", tmp])
@@ -162,7 +168,7 @@ def build_decode_extension(force: bool = False) -> str:
 
 
 def build_machine_extension(force: bool = False) -> str:
-    if not force and _fresh(MACHINE_OUT, [MACHINE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(MACHINE_OUT, [MACHINE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return MACHINE_OUT
     tmp = MACHINE_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, MACHINE_SRC, "-o", tmp])
@@ -171,7 +177,7 @@ def build_machine_extension(force: bool = False) -> str:
 
 
 def build_carlier_extension(force: bool = False) -> str:
-    if not force and _fresh(CARLIER_OUT, [CARLIER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(CARLIER_OUT, [CARLIER_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return CARLIER_OUT
     tmp = CARLIER_OUT + f".tmp{os.getpid()}"
     subprocess.check_call([hipcc(), *FLAGS, CARLIER_SRC, "-o", tmp])
@@ -179,8 +185,17 @@ def build_carlier_extension(force: bool = False) -> str:
     return CARLIER_OUT
 
 
+def build_propagate_extension(force: bool = False) -> str:
+    if not force and _fresh(PROPAGATE_OUT, [PROPAGATE_SRC, _CHECKS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
+        return PROPAGATE_OUT
+    tmp = PROPAGATE_OUT + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, PROPAGATE_SRC, "-o", tmp])
+    os.replace(tmp, PROPAGATE_OUT)
+    return PROPAGATE_OUT
+
+
 def build_cpu_twin(force: bool = False) -> str:
-    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER]):
+    if not force and _fresh(CPU_OUT, [CPU_SRC, _CHECKS, _ROWS, _HEADER, _SEARCH, _RULES, _KEYS, _BEAM, _BOUND, _ORDER, _TABU, _BLOCK, _RELINK, _DECODE, _MACHINE, _CARLIER, _PROPAGATE]):
         return CPU_OUT
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -22,6 +22,7 @@
 #include "jss_decode.h"
 #include "jss_machine.h"
 #include "jss_carlier.h"
+#include "jss_propagate.h"
 
 namespace jss_abi {
 
@@ -521,6 +522,28 @@ inline int bottleneck_exact_check(const JssDesc *d, const JssState *s, const Jss
     if (b->reopt < 0 || b->reopt > JSS_BOTTLENECK_MAX_REOPT) return JSS_E_SHAPE;
     if (b->nodes < 1 || b->nodes > JSS_CARLIER_MAX_NODES) return JSS_E_SHAPE;
     return carlier_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
+}
+
+// ---- constraint propagation on operation windows (include/jss_propagate.h) -------------------------------------------------------
+// What libjss_propagate_hip.so keeps in LDS for one candidate: the op row, the rank row and both generations of est and of lct
+// (int32) and three rows of machine-sorted sequences (uint16) over the entries of a [jmax][mmax] row rounded up to a multiple of
+// 8, and four blocks of one word per machine.
+inline long long propagate_lds_bytes(int jmax, int mmax) { return 30 * order_entries8(jmax, mmax) + 4 * 64 * 4; }
+
+// jss_propagate (libjss_propagate_hip.so and the twin): the batch as jss_order_eval checks it
+inline int propagate_check(const JssDesc *d, const JssState *s, const JssPropagate *r) {
+    if (!d || !s || !r) return JSS_E_NULL;
+    const int rc = check_args(d, s, nullptr, false);
+    if (rc) return rc;
+    if (!r->status || !r->ub || (!r->rank && r->fixed) || !r->est_in != !r->lct_in) return JSS_E_NULL;
+    if (!r->hyp_op != !r->hyp_est || !r->hyp_op != !r->hyp_lct) return JSS_E_NULL;
+    if (r->est && (r->est == r->est_in || r->est == r->lct_in)) return JSS_E_NULL;
+    if (r->lct && (r->lct == r->est_in || r->lct == r->lct_in)) return JSS_E_NULL;
+    if (r->n < 0 || (!r->parents && r->n != d->batch)) return JSS_E_SHAPE;
+    if (r->passes < 1 || r->passes > JSS_PROPAGATE_MAX_PASSES) return JSS_E_SHAPE;
+    if (r->stride != 0 && r->stride != d->jmax * d->mmax) return JSS_E_SHAPE;
+    if (r->win_stride != 0 && r->win_stride != d->jmax * d->mmax) return JSS_E_SHAPE;
+    return propagate_lds_bytes(d->jmax, d->mmax) > kOrderLdsLimit ? JSS_E_LDS : 0;
 }
 
 // jss_error_string's text for 0 and the argument codes; nullptr for any other code (each library words those itself)

@@ -2599,3 +2599,130 @@ int jss_bottleneck_exact(const JssDesc *desc, const JssState *state, const JssBo
 }
 
 }  // extern "C"
+
+// ---- constraint propagation on operation windows (include/jss_propagate.h) ------------------------------------------------------
+namespace {
+
+// The header's passes on a relaxed MachineProblem: est and lct by flat index, a Jacobi step per call of pass().  Rule 4 is
+// evaluated per receiving operation by two sweeps per threshold -- descending est under every upper end, ascending lct over
+// every lower end -- whose running sets are the header's task intervals W (and subsets and pairs of thresholds that W of a
+// counting pair dominates: the same deduction under a weaker condition).
+struct Propagator {
+    const MachineProblem &w;
+    const uint64_t fixed;
+    std::vector<int32_t> est, lct, new_est, new_lct;
+    std::vector<int> pos, by_est, by_lct;
+
+    Propagator(const MachineProblem &problem, uint64_t mask) : w(problem), fixed(mask) {}
+
+    bool closed() const {
+        for (int j = 0; j < w.J; ++j)
+            for (int k = 0; k < w.M; ++k)
+                if (est[j * w.mmax + k] + w.dur(j * w.mmax + k) > lct[j * w.mmax + k]) return true;
+        return false;
+    }
+
+    // one pass: 1 refuted, 0 nothing moved, 2 something moved
+    int pass() {
+        new_est = est, new_lct = lct;
+        bool over = false;
+        for (int j = 0; j < w.J; ++j)
+            for (int k = 0; k < w.M; ++k) {
+                const int x = j * w.mmax + k;
+                if (k > 0) new_est[x] = std::max(new_est[x], est[x - 1] + w.dur(x - 1));
+                if (k + 1 < w.M) new_lct[x] = std::min(new_lct[x], lct[x + 1] - w.dur(x + 1));
+                if (w.before[x] >= 0) new_est[x] = std::max(new_est[x], est[w.before[x]] + w.dur(w.before[x]));
+                if (w.behind[x] >= 0) new_lct[x] = std::min(new_lct[x], lct[w.behind[x]] - w.dur(w.behind[x]));
+            }
+        for (int m = 0; m < JSS_MAX_MACHINES; ++m) {
+            if ((fixed >> m & 1) || w.on[m].empty()) continue;
+            pos.clear();
+            for (int x : w.on[m])
+                if (w.dur(x) > 0) pos.push_back(x);
+            by_est = pos, by_lct = pos;
+            std::sort(by_est.begin(), by_est.end(), [&](int x, int y) { return est[x] != est[y] ? est[x] > est[y] : x < y; });
+            std::sort(by_lct.begin(), by_lct.end(), [&](int x, int y) { return lct[x] != lct[y] ? lct[x] < lct[y] : x < y; });
+            for (int x : pos) {
+                const int ex = est[x], lx = lct[x], dx = w.dur(x);
+                int ne = new_est[x], nl = new_lct[x];
+                for (int y : pos) {
+                    if (y == x) continue;
+                    if (ex + dx + w.dur(y) > lct[y]) ne = std::max(ne, est[y] + w.dur(y));
+                    if (est[y] + w.dur(y) + dx > lx) nl = std::min(nl, lct[y] - w.dur(y));
+                }
+                for (int b : pos) {
+                    const int L = lct[b];
+                    int P = 0, E = INT32_MIN;
+                    for (int y : by_est) {
+                        if (lct[y] <= L) P += w.dur(y), E = std::max(E, est[y] + P);
+                        if (!P) continue;
+                        const int e = est[y];
+                        over |= e + P > L;
+                        if ((ex < e || lx > L) && std::min(e, ex) + P + dx > L) ne = std::max(ne, E);
+                    }
+                }
+                for (int a : pos) {
+                    const int e = est[a];
+                    int P = 0, F = INT32_MAX;
+                    for (int y : by_lct) {
+                        if (est[y] >= e) P += w.dur(y), F = std::min(F, lct[y] - P);
+                        if (!P) continue;
+                        const int L = lct[y];
+                        if ((ex < e || lx > L) && e + P + dx > std::max(L, lx)) nl = std::min(nl, F);
+                    }
+                }
+                new_est[x] = ne, new_lct[x] = nl;
+            }
+        }
+        const bool moved = new_est != est || new_lct != lct;
+        est.swap(new_est), lct.swap(new_lct);
+        return over || closed() ? 1 : moved ? 2 : 0;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int jss_propagate(const JssDesc *desc, const JssState *state, const JssPropagate *prop, void *) {
+    if (const int rc = propagate_check(desc, state, prop)) return rc;
+    const JssDesc d = *desc;
+    const JssPropagate t = *prop;
+    const int region = d.jmax * d.mmax;
+    auto in_range = [](int v) { return v >= 0 && v <= JSS_PROPAGATE_MAX_TIME; };
+    auto one = [&](int c) {
+        const uint64_t fixed = t.fixed ? t.fixed[c] : 0;
+        const int32_t *rank = t.rank ? t.rank + (size_t)c * t.stride : nullptr;
+        const int32_t *est_in = t.est_in ? t.est_in + (size_t)c * t.win_stride : nullptr;
+        const int32_t *lct_in = t.lct_in ? t.lct_in + (size_t)c * t.win_stride : nullptr;
+        MachineProblem w;
+        if (!w.open(d, state, t.parents ? t.parents[c] : c, fixed) || w.negative_rank(rank, fixed)) return void(t.status[c] = -1);
+        const int ub = t.ub[c], hyp = t.hyp_op ? t.hyp_op[c] : -1;
+        bool ok = in_range(ub);
+        if (hyp >= 0) ok = ok && hyp < region && hyp / d.mmax < w.J && hyp % d.mmax < w.M && in_range(t.hyp_est[c]) && in_range(t.hyp_lct[c]);
+        for (int j = 0; est_in && j < w.J; ++j)
+            for (int k = 0; k < w.M; ++k) ok = ok && in_range(est_in[j * d.mmax + k]) && in_range(lct_in[j * d.mmax + k]);
+        if (!ok) return void(t.status[c] = -1);
+        if (w.relax(rank, fixed) < 0) return void(t.status[c] = -2);
+        Propagator p(w, fixed);
+        p.est.assign((size_t)region, 0), p.lct.assign((size_t)region, 0);
+        for (int j = 0; j < w.J; ++j)
+            for (int k = 0; k < w.M; ++k) {
+                const int x = j * d.mmax + k;
+                p.est[x] = w.head[x], p.lct[x] = ub - w.tail[x];
+                if (est_in) p.est[x] = std::max(p.est[x], est_in[x]), p.lct[x] = std::min(p.lct[x], lct_in[x]);
+                if (x == hyp) p.est[x] = std::max(p.est[x], t.hyp_est[c]), p.lct[x] = std::min(p.lct[x], t.hyp_lct[c]);
+            }
+        int status = p.closed() ? JSS_PROPAGATE_REFUTED : JSS_PROPAGATE_BUDGET, used = 0;
+        while (status == JSS_PROPAGATE_BUDGET && used < t.passes) ++used, status = p.pass();
+        t.status[c] = status;
+        if (t.passes_used) t.passes_used[c] = used;
+        if (status == JSS_PROPAGATE_REFUTED) return;
+        if (t.est) w.write_row(t.est + (size_t)c * region, d.jmax, p.est.data());
+        if (t.lct) w.write_row(t.lct + (size_t)c * region, d.jmax, p.lct.data());
+    };
+    parallel_for<true>(t.n, d.threads, one);
+    return 0;
+}
+
+}  // extern "C"

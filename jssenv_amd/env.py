@@ -1490,6 +1490,96 @@ class BatchedJssEnv:
             self._machine_keep = [r, par, fx, bs]              # alive until the launch has read them
         return (mk, out, info, fixed_order) if order else (mk, out, info)
 
+    # -- constraint propagation on operation windows (include/jss_propagate.h) -------------------------------------------------------
+    def propagate(self, ub, rank=None, fixed=0, parents=None, est=None, lct=None, hyp=None, passes: int = 256, windows: bool = False):
+        """Constraint propagation on the windows [earliest start, latest completion] of every operation of a partial selection
+        under the trial makespan ``ub``, one candidate per wavefront in one launch (``jss_propagate``; include/jss_propagate.h
+        defines the rules and their Jacobi passes; integers, the same bits on every backend).  ``rank``, ``fixed`` and ``parents``
+        are ``relax_machines``'s.  ``ub`` is an int or ``(n,)``; ``est`` and ``lct``, given together, are windows to start from,
+        int32 ``(jmax, mmax)`` -- one table for all -- or ``(n, jmax, mmax)``; ``hyp`` is a tuple of three ``(n,)`` arrays, the
+        flat index ``j * mmax + k`` of one operation per candidate (-1: none) and the window it is held to; ``passes`` lies in
+        [1, 4096].
+
+        Returns ``(status, passes_used)``, each (n,) int32 -- status 0: a fixpoint, 1: refuted (no schedule of the selection with
+        a makespan of at most ``ub`` exists under the hypothesis), 2: the budget of passes is spent, -1 refused, -2 cyclic -- and
+        with ``windows`` also ``est`` and ``lct`` (n, jmax, mmax), -1 in the padding and in the rows of candidates that did not
+        end with status 0 or 2.  Arrays of the env's backend."""
+        from .search import propagate_library
+        be = self.backend
+        lib = propagate_library(be)
+        if not 1 <= int(passes) <= _abi.PROPAGATE_MAX_PASSES:
+            raise ValueError(f"propagate: passes must lie in [1, {_abi.PROPAGATE_MAX_PASSES}]")
+        if (est is None) != (lct is None):
+            raise ValueError("propagate: est and lct are given together")
+        if hyp is not None and len(hyp) != 3:
+            raise ValueError("propagate: hyp is a tuple of three (n,) arrays: the operation, its est and its lct")
+        region = self.jmax * self.mmax
+        with be.on_device():
+
+            def table(x, what):
+                if x is None:
+                    return None, None
+                x = be.as_device(x, "int32")
+                if getattr(be, "torch", None) is None:
+                    x = x.copy()                                       # (as_device keeps ONE array alive)
+                shape = tuple(x.shape)
+                if not (shape == (self.jmax, self.mmax) or (len(shape) == 3 and shape[1:] == (self.jmax, self.mmax))):
+                    raise ValueError(f"propagate: {what} must have shape {(self.jmax, self.mmax)} or (n, {self.jmax}, {self.mmax}), got {shape}")
+                return x, shape
+
+            r, shape = table(rank, "rank")
+            e_in, e_shape = table(est, "est")
+            l_in, l_shape = table(lct, "lct")
+            if e_shape != l_shape:
+                raise ValueError("propagate: est and lct must have the same shape")
+            counts = [s[0] for s in (shape, e_shape) if s and len(s) == 3]
+            if np.ndim(ub) == 1:
+                counts.append(len(ub))
+            if hyp is not None:
+                counts.append(len(hyp[0]))
+            par, n = self._machine_call_start("propagate", parents, counts[0] if counts else None, fixed)
+            if any(x != n for x in counts):
+                raise ValueError(f"propagate: {counts} tables or entries for {n} candidates")
+            masks = self._fixed_masks(fixed, n, "propagate")
+            if r is None and masks.any():
+                raise ValueError("propagate: a fixed machine needs a rank")
+            fx = be.from_numpy(masks.view(np.int64)) if masks.any() else None
+
+            def row(x, what):
+                if hasattr(x, "detach") and getattr(be, "torch", None) is not None and x.dtype == be.torch.int32:
+                    if tuple(x.shape) != (n,):                         # (an int32 tensor stays where it is: no copy through the host)
+                        raise ValueError(f"propagate: {what} must be {(n,)} integers")
+                    return be.as_device(x, "int32")
+                x = np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x)
+                if x.ndim == 0 and what == "ub":
+                    x = np.full(n, int(x))
+                if x.shape != (n,) or x.dtype.kind not in "iu":
+                    raise ValueError(f"propagate: {what} must be {(n,)} integers")
+                if x.size and (x.min() < -2 ** 31 or x.max() >= 2 ** 31):
+                    raise ValueError(f"propagate: {what} must fit 32 bits")
+                return be.from_numpy(np.ascontiguousarray(x, dtype=np.int32))
+
+            u = row(ub, "ub")
+            h = [None] * 3 if hyp is None else [row(x, "hyp") for x in hyp]
+
+            def out(*shape):
+                x = be.zeros(shape, "int32")
+                x -= 1
+                return x
+
+            status, used = out(n), out(n)
+            e_out, l_out = (out(n, self.jmax, self.mmax), out(n, self.jmax, self.mmax)) if windows else (None, None)
+            if n:
+                p = be.ptr
+                arg = _abi.JssPropagate(n, region if shape and len(shape) == 3 else 0, region if e_shape and len(e_shape) == 3 else 0,
+                                        int(passes), p(par), p(r), p(fx), p(u), p(e_in), p(l_in), p(h[0]), p(h[1]), p(h[2]), p(status),
+                                        p(used), p(e_out), p(l_out))
+                rc = lib.jss_propagate(C.byref(self._desc), C.byref(self._state), C.byref(arg), be.stream())
+                if rc:
+                    _abi.check(be.lib, rc, "jss_propagate")
+            self._machine_keep = [r, par, fx, u, e_in, l_in] + h  # alive until the launch has read them
+        return (status, used, e_out, l_out) if windows else (status, used)
+
     def pilot_step(self, kind: Union[str, int] = "SPT", seed: Optional[int] = None, autoreset: bool = False, weights=None,
                    keys=None, nope_key=None):
         """One step of the pilot method: every action of every env is scored by ``lookahead(kind)`` (the action, then the

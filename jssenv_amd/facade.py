@@ -459,6 +459,19 @@ class JssEnv(gymnasium_base("Env")):
         host = [np.asarray(b.backend.numpy(x))[0] for x in out]
         return (int(host[0]),) + tuple(host[1:])
 
+    def propagate(self, ub, rank=None, fixed: int = 0, est=None, lct=None, hyp=None, passes: int = 256, windows: bool = False):
+        """The B = 1 form of ``BatchedJssEnv.propagate`` (include/jss_propagate.h): constraint propagation on the operation windows
+        of the partial selection ``(rank, fixed)`` under the trial makespan ``ub``, from the windows ``est`` and ``lct`` (J x M or
+        jmax x mmax) where given and under the hypothesis ``hyp = (flat index j * mmax + k, est, lct)`` on one operation.  Returns
+        ``(status, passes_used)``, ints (status 0 a fixpoint, 1 refuted, 2 the budget is spent, -1 refused, -2 cyclic), then with
+        ``windows`` ``est`` and ``lct`` (jmax, mmax), host arrays."""
+        b = self._b
+        out = b.propagate(int(ub), None if rank is None else self._machine_row(rank), int(fixed), None,
+                          None if est is None else self._machine_row(est), None if lct is None else self._machine_row(lct),
+                          None if hyp is None else tuple(np.asarray([int(x)], np.int32) for x in hyp), passes, windows)
+        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        return tuple(int(x) for x in host[:2]) + tuple(host[2:])
+
     def render(self, mode: str = "human"):
         """Gantt chart of ``solution`` (jss_env.py:655-693); needs pandas + plotly on the host."""
         from .render import gantt

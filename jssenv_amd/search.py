@@ -40,6 +40,10 @@ and ``brkga_search`` is ``relax_machines()`` of the empty selection, a stronger 
 And Carlier's branch and bound for those one-machine problems (include/jss_carlier.h): ``carlier_reference``, the search itself,
 ``solve_reference`` and ``bottleneck_exact_reference``, the NumPy mirrors of ``jss_machine_solve`` and ``jss_bottleneck_exact`` and
 their executable definition, ``carlier_library``, ``bottleneck_search(nodes=...)`` and ``target="one_machine_exact"``.
+
+And constraint propagation on operation windows (include/jss_propagate.h): ``propagate_reference``, the NumPy mirror of
+``jss_propagate`` and its executable definition, ``propagate_library``, ``destructive_bound`` -- trial makespans scanned upward and
+shaved on the device -- with ``destructive_reference``, the same loop over the mirror, and ``target="destructive"``.
 """
 from __future__ import annotations
 
@@ -1075,9 +1079,10 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine", "one_machine_exact"):
-            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
-        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine" else env.solve_machines()[0]
+        if target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
+            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
+        tgt = (env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
+               else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, W))
     elif target is None:
         tgt = None
     else:
@@ -1161,9 +1166,10 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
     be = env.backend
     env.reset()
     if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine", "one_machine_exact"):
-            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
-        tgt = env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine" else env.solve_machines()[0]
+        if target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
+            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
+        tgt = (env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
+               else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, W))
     elif target is None:
         tgt = None
     else:
@@ -1354,6 +1360,7 @@ class BrkgaResult:
     generations: int
     optimal: np.ndarray
     env: Optional[BatchedJssEnv] = None
+    target: Optional[np.ndarray] = None          # (G,), the target the search stopped at; None without one
 
 
 def brkga_search(instances, population=256, generations=100, elite=0.15, mutants=0.15, rho=0.7, delta=0.5, seed_rules=("SPT", "MWR"),
@@ -1401,8 +1408,8 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     rules = tuple(seed_rules or ())
     if len(rules) > P:
         raise ValueError("brkga_search: more seed rules than individuals")
-    if isinstance(target, str) and target not in ("lower_bound", "one_machine", "one_machine_exact"):
-        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', None, an int or one int per instance")
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
+        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
     S = G * P
     kw = dict(device=device) if _backend is None else dict(_backend=_backend)
 
@@ -1418,7 +1425,7 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     if isinstance(target, str):
         tgt = host(env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
-                   else env.solve_machines()[0]).astype(np.int32)
+                   else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, 1)).astype(np.int32)
     elif target is None:
         tgt = None
     else:
@@ -1471,7 +1478,7 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
         rank_out = start_out.copy()
     return BrkgaResult(makespan=mk[winner], keys=host(keys)[winner].copy(), start=start_out, rank=rank_out,
                        history=np.stack([host(h) for h in history], axis=1).astype(np.int32), generations=t,
-                       optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, env=env)
+                       optimal=np.zeros(G, bool) if tgt is None else mk[winner] <= tgt, env=env, target=tgt)
 
 
 # ---- one-machine relaxations of partial selections, the shifting bottleneck construction (include/jss_machine.h) ----------------
@@ -1701,8 +1708,8 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
         raise ValueError("bottleneck_search: spread in [0, 2**30), polish >= 0")
     if not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
         raise ValueError(f"bottleneck_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}]")
-    if isinstance(target, str) and target not in ("lower_bound", "one_machine") + (("one_machine_exact",) if nodes else ()):
-        raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', None, an int or one int per instance"
+    if isinstance(target, str) and target not in ("lower_bound", "one_machine", "destructive") + (("one_machine_exact",) if nodes else ()):
+        raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', 'destructive', None, an int or one int per instance"
                          " ('one_machine_exact' with nodes > 0)")
     if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
         raise NotImplementedError("bottleneck_search takes instances (a name, a path, an Instance, or a list of them): call "
@@ -1726,7 +1733,8 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     bound = host(env.solve_machines(nodes=nodes)[0] if nodes else env.relax_machines()[0]).astype(np.int32)
     if isinstance(target, str):
-        tgt = bound.copy() if target != "lower_bound" else host(env.lower_bound()).astype(np.int32)
+        tgt = (host(env.lower_bound()).astype(np.int32) if target == "lower_bound" else _destructive_target(env, G, 1) if target == "destructive"
+               else bound.copy())
     elif target is None:
         tgt = None
     else:
@@ -1942,3 +1950,334 @@ def bottleneck_exact_reference(env_const, ops, parents=None, bias=None, reopt=1,
         info[c] = (fixed_here, tried, shorter, first, count["total"], count["most"], count["open"], count["replaced"])
         order[c] = (seq + [-1] * mmax)[:mmax]
     return makespan, rank_o, info, order
+
+
+# ---- constraint propagation on operation windows, destructive lower bounds (include/jss_propagate.h) ---------------------------
+PROPAGATE_RULES = ("job", "fixed", "pairs", "overload", "after", "before")
+
+
+def propagate_library(backend):
+    """The library of ``backend`` that exports include/jss_propagate.h: ``backend.propagate_lib`` (HipBackend:
+    libjss_propagate_hip.so, CpuBackend: the twin), else ``backend.lib`` where it exports the call."""
+    lib = getattr(backend, "propagate_lib", None)
+    if lib is None:
+        lib = backend.lib
+        if not all(hasattr(lib, name) for name in _abi.PROPAGATE_SYMBOLS):
+            raise RuntimeError("propagate: the backend's library does not export include/jss_propagate.h")
+        _abi.bind_propagate(lib)
+    return lib
+
+
+def _task_intervals(est, lct, d, rules, slack):
+    """Rule 4 of include/jss_propagate.h on one free machine's operations of positive duration, as the header states it: every
+    pair (a, b), its set W, the overload test and the bounds that "after" and "before" give every operation outside W.  Returns
+    ``(overload, est deductions, lct deductions)``."""
+    n = est.size
+    inside = (est[None, None, :] >= est[:, None, None]) & (lct[None, None, :] <= lct[None, :, None])        # [a, b, x]
+    idx = np.arange(n)
+    counts = inside[idx, :, idx] & inside[:, idx, idx]                                                        # a in W and b in W
+    P = (inside * d).sum(axis=2)
+    over = bool((counts & (est[:, None] + P + slack > lct[None, :])).any()) if "overload" in rules else False
+    new_est, new_lct = est.copy(), lct.copy()
+    weights = (inside * d).reshape(n * n, n).astype(np.float64)
+    # [a, b, x]: the sum of d over {y in W(a, b) : with[x, y]}, one matrix product (in doubles, which hold these sums exactly)
+    sums = lambda with_: np.rint(weights @ with_.T.astype(np.float64)).astype(np.int64).reshape(n, n, n)   # noqa: E731
+    if "after" in rules:
+        later = (est[None, :] >= est[:, None]).astype(np.int64)                                               # [x, y]: est_y >= est_x
+        ends = np.where(inside, est[None, None, :] + sums(later), -2 ** 62).max(axis=2)
+        hit = counts[:, :, None] & ~inside & (np.minimum(est[:, None, None], est[None, None, :]) + P[:, :, None] + d[None, None, :]
+                                              > lct[None, :, None])
+        new_est = np.maximum(new_est, np.where(hit, ends[:, :, None], -2 ** 62).max(axis=(0, 1)))
+    if "before" in rules:
+        sooner = (lct[None, :] <= lct[:, None]).astype(np.int64)                                              # [x, y]: lct_y <= lct_x
+        begins = np.where(inside, lct[None, None, :] - sums(sooner), 2 ** 62).min(axis=2)
+        hit = counts[:, :, None] & ~inside & (est[:, None, None] + P[:, :, None] + d[None, None, :]
+                                              > np.maximum(lct[None, :, None], lct[None, None, :]))
+        new_lct = np.minimum(new_lct, np.where(hit, begins[:, :, None], 2 ** 62).min(axis=(0, 1)))
+    return over, new_est, new_lct
+
+
+def propagate_reference(env_const, ops, ub, rank=None, fixed=None, parents=None, est=None, lct=None, hyp=None, passes=256, fill=-1,
+                        rules=PROPAGATE_RULES, _overload_slack=0):
+    """include/jss_propagate.h's jss_propagate on host arrays, the plain restatement of the header's definition, one candidate
+    after the other: ``machine_reference`` for what the header takes from jss_machine.h, then Jacobi passes of the rules.
+    ``ub`` an int or (n,); ``est`` / ``lct`` (jmax, mmax), one table for all, or (n, jmax, mmax), or None; ``hyp`` three (n,) arrays
+    or None; the rest as in ``machine_reference``.  ``rules`` names the rules that are applied (all of them: the definition; fewer
+    tell what a rule contributes).  Returns ``(status, passes_used, est, lct)``: int32 (n,) twice, (n, jmax, mmax) twice; rows
+    that the call does not write hold ``fill``."""
+    const = np.asarray(env_const, dtype=np.int64).reshape(-1, _abi.NC)
+    B = const.shape[0]
+    if rank is not None:
+        rank = np.asarray(rank, dtype=np.int64)
+        jmax, mmax = rank.shape[-2:]
+    else:
+        jmax, mmax = np.asarray(ops).shape[-2:]
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, jmax, mmax)
+    est_in = None if est is None else np.asarray(est, dtype=np.int64)
+    lct_in = None if lct is None else np.asarray(lct, dtype=np.int64)
+    sizes = [len(parents) if parents is not None else None, rank.shape[0] if rank is not None and rank.ndim == 3 else None,
+             None if fixed is None or np.ndim(fixed) == 0 else len(fixed), est_in.shape[0] if est_in is not None and est_in.ndim == 3 else None,
+             len(ub) if np.ndim(ub) == 1 else None, len(hyp[0]) if hyp is not None else None, B]
+    n = next(x for x in sizes if x is not None)
+    par = np.arange(n) if parents is None else np.asarray(parents, dtype=np.int64)
+    masks = [0] * n if fixed is None else [int(fixed) & (2 ** 64 - 1)] * n if np.ndim(fixed) == 0 else [int(x) & (2 ** 64 - 1) for x in fixed]
+    ubs = np.broadcast_to(np.asarray(ub, dtype=np.int64), (n,))
+    status, used = np.full(n, fill, np.int32), np.full(n, fill, np.int32)
+    est_o, lct_o = np.full((n, jmax, mmax), fill, np.int32), np.full((n, jmax, mmax), fill, np.int32)
+    ok = lambda v: 0 <= int(v) <= _abi.PROPAGATE_MAX_TIME   # noqa: E731
+    for c in range(n):
+        row = None if rank is None else rank[c] if rank.ndim == 3 else rank
+        res = machine_reference(const, ops, None if row is None else row[None], [masks[c]], par[c:c + 1])
+        status[c] = -1
+        if res[0][0] == -1:
+            continue
+        i = int(par[c])
+        J, M, tab = (int(const[i, x]) for x in (_abi.C_JOBS, _abi.C_MACHINES, _abi.C_TABLE))
+        mach, d = ((ops[tab] >> 16) & 63)[:J, :M], (ops[tab] & 0xFFFF)[:J, :M]
+        e_in = None if est_in is None else (est_in[c] if est_in.ndim == 3 else est_in)[:J, :M]
+        l_in = None if lct_in is None else (lct_in[c] if lct_in.ndim == 3 else lct_in)[:J, :M]
+        h = -1 if hyp is None else int(hyp[0][c])
+        if not ok(ubs[c]) or (e_in is not None and not (all(ok(v) for v in e_in.reshape(-1)) and all(ok(v) for v in l_in.reshape(-1)))):
+            continue
+        if h >= 0 and not (h < jmax * mmax and h // mmax < J and h % mmax < M and ok(hyp[1][c]) and ok(hyp[2][c])):
+            continue
+        if res[0][0] == -2:
+            status[c] = -2
+            continue
+        e = res[5][0, :J, :M].astype(np.int64)
+        l = int(ubs[c]) - res[6][0, :J, :M].astype(np.int64)   # noqa: E741
+        if e_in is not None:
+            e, l = np.maximum(e, e_in), np.minimum(l, l_in)   # noqa: E741
+        if h >= 0:
+            e[h // mmax, h % mmax] = max(e[h // mmax, h % mmax], int(hyp[1][c]))
+            l[h // mmax, h % mmax] = min(l[h // mmax, h % mmax], int(hyp[2][c]))
+        # the arcs of the fixed machines, and the free machines' operations of positive duration
+        arcs, free = [], []
+        for m in sorted(set(mach.reshape(-1).tolist())):
+            its = [(j, k) for j in range(J) for k in range(M) if mach[j, k] == m]
+            if masks[c] >> m & 1:
+                seq = sorted(its, key=lambda o: (row[o[0]][o[1]], o))
+                arcs += list(zip(seq[:-1], seq[1:]))
+            else:
+                its = [o for o in its if d[o] > 0]
+                if its:
+                    free.append((np.array([o[0] for o in its]), np.array([o[1] for o in its])))
+        state, count = _abi.PROPAGATE_REFUTED if (e + d > l).any() else _abi.PROPAGATE_BUDGET, 0
+        while state == _abi.PROPAGATE_BUDGET and count < int(passes):
+            count += 1
+            ne, nl, over = e.copy(), l.copy(), False
+            if "job" in rules:
+                ne[:, 1:] = np.maximum(ne[:, 1:], (e + d)[:, :-1])
+                nl[:, :-1] = np.minimum(nl[:, :-1], (l - d)[:, 1:])
+            if "fixed" in rules:
+                for u, v in arcs:
+                    ne[v] = max(ne[v], e[u] + d[u])
+                    nl[u] = min(nl[u], l[v] - d[v])
+            for js, ks in free:
+                ee, ll, dd = e[js, ks], l[js, ks], d[js, ks]
+                if "pairs" in rules:
+                    never = (ee[:, None] + dd[:, None] + dd[None, :] > ll[None, :]) & ~np.eye(ee.size, dtype=bool)    # [i, j]: i cannot precede j
+                    ne[js, ks] = np.maximum(ne[js, ks], np.where(never, (ee + dd)[None, :], -2 ** 62).max(axis=1))
+                    nl[js, ks] = np.minimum(nl[js, ks], np.where(never, (ll - dd)[:, None], 2 ** 62).min(axis=0))
+                o, te, tl = _task_intervals(ee, ll, dd, rules, int(_overload_slack))
+                over = over or o
+                ne[js, ks], nl[js, ks] = np.maximum(ne[js, ks], te), np.minimum(nl[js, ks], tl)
+            moved = not (np.array_equal(ne, e) and np.array_equal(nl, l))
+            e, l = ne, nl   # noqa: E741
+            state = _abi.PROPAGATE_REFUTED if over or (e + d > l).any() else _abi.PROPAGATE_BUDGET if moved else _abi.PROPAGATE_FIXPOINT
+        status[c], used[c] = state, count
+        if state != _abi.PROPAGATE_REFUTED:
+            est_o[c], lct_o[c] = -1, -1
+            est_o[c, :J, :M], lct_o[c, :J, :M] = e, l
+    return status, used, est_o, lct_o
+
+
+@dataclass
+class DestructiveResult:
+    """What ``destructive_bound`` returns, one entry per instance: ``lower_bound`` (G,), the first trial makespan that neither
+    propagation nor shaving refuted (never above ``upper``); ``first_bound`` (G,), the scan's: the first that propagation alone
+    left open; ``one_machine`` (G,), ``solve_machines()[0]`` of the empty selection, where the scan began; ``est`` and ``lct`` (G,
+    jmax, mmax), the windows at ``lower_bound`` (-1 in the padding; -1 everywhere where ``upper`` itself was refuted); ``launches``
+    and ``propagations`` (G,), the calls of ``propagate`` and their candidates; ``proved_optimal`` (G,): the bound reached
+    ``upper``."""
+    lower_bound: np.ndarray
+    first_bound: np.ndarray
+    one_machine: np.ndarray
+    est: np.ndarray
+    lct: np.ndarray
+    launches: np.ndarray
+    propagations: np.ndarray
+    proved_optimal: np.ndarray
+    env: Optional[object] = None
+
+
+def _destructive_scan(prop, start, upper, span):
+    """the first trial makespan from ``start`` on that ``prop(ubs)`` -> (status, est, lct) does not refute, ``span`` of them per
+    call and none at or above ``upper``: (bound, est, lct or None twice, launches, propagations)"""
+    U, launches, count = int(start), 0, 0
+    while upper is None or U < upper:
+        ubs = U + np.arange(span, dtype=np.int64)
+        if upper is not None:
+            ubs = ubs[ubs < upper]
+        status, est, lct = prop(ubs)
+        launches, count = launches + 1, count + ubs.size
+        left = np.flatnonzero(status != _abi.PROPAGATE_REFUTED)
+        if left.size:
+            return int(ubs[left[0]]), est[left[0]].copy(), lct[left[0]].copy(), launches, count
+        U += ubs.size
+    return int(upper), None, None, launches, count
+
+
+def shaving_hypotheses(est, lct, dur):
+    """One shaving round's candidates on the window tables ``est`` / ``lct`` (jmax, mmax; -1 in the padding) with the durations
+    ``dur``: two per operation whose window holds more than one start, "the start is at most mid" and "at least mid + 1", mid the
+    middle of its starts.  Returns ``(ops, mid, d, hyp)``: the operations' flat indices, their middles and durations, and the
+    three (2 * len(ops),) arrays ``BatchedJssEnv.propagate`` takes as ``hyp``."""
+    late = lct - dur                                                   # the latest starts
+    ops = np.flatnonzero(((est >= 0) & (late > est)).reshape(-1))
+    e, s, d = est.reshape(-1)[ops].astype(np.int64), late.reshape(-1)[ops].astype(np.int64), dur.reshape(-1)[ops].astype(np.int64)
+    mid = (e + s) // 2
+    hyp = (np.repeat(ops, 2).astype(np.int32), np.stack([e, mid + 1], axis=1).reshape(-1).astype(np.int32),
+           np.stack([mid + d, s + d], axis=1).reshape(-1).astype(np.int32))
+    return ops, mid, d, hyp
+
+
+def _destructive_loop(prop, dur, one_machine, upper, shave, rounds, span):
+    """``destructive_bound``'s loop on one instance.  ``prop(ubs, est=None, lct=None, hyp=None)`` propagates one candidate per
+    entry of ``ubs`` -- from the shared tables ``est`` / ``lct`` and under the hypotheses ``hyp`` where given -- and returns host
+    arrays ``(status, est, lct)``; ``dur`` (jmax, mmax) holds the durations."""
+    upper = None if upper is None else int(upper)
+    U, est, lct, launches, count = _destructive_scan(prop, one_machine if upper is None else min(one_machine, upper), upper, span)
+    first = U
+    while shave and est is not None and (upper is None or U < upper):
+        dead = False
+        for _ in range(int(rounds)):
+            ops, mid, d, hyp = shaving_hypotheses(est, lct, dur)
+            if not ops.size:
+                break
+            status = prop(np.full(2 * ops.size, U, np.int64), est, lct, hyp)[0]
+            launches, count = launches + 1, count + 2 * ops.size
+            gone = (status == _abi.PROPAGATE_REFUTED).reshape(-1, 2)
+            dead = bool(gone.all(axis=1).any())
+            if dead or not gone.any():
+                break
+            est, lct = est.copy(), lct.copy()
+            low, high = gone[:, 0], gone[:, 1]
+            est.reshape(-1)[ops[low]] = (mid + 1)[low]                 # the lower half is refuted: the start lies above mid
+            lct.reshape(-1)[ops[high]] = (mid + d)[high]               # the upper half is refuted: the start lies at or below mid
+            status, new_est, new_lct = prop(np.full(1, U, np.int64), est, lct)
+            launches, count = launches + 1, count + 1
+            dead = status[0] == _abi.PROPAGATE_REFUTED
+            if dead:
+                break
+            est, lct = new_est[0].copy(), new_lct[0].copy()
+        if not dead:
+            break
+        U, est, lct, more, n = _destructive_scan(prop, U + 1, upper, 1)  # U is refuted: on from U + 1, where shaving starts anew
+        launches, count = launches + more, count + n
+    if est is None:                                                    # the bound is `upper`, which was not propagated
+        status, e, l = prop(np.full(1, U, np.int64))   # noqa: E741
+        launches, count = launches + 1, count + 1
+        fill = status[0] == _abi.PROPAGATE_REFUTED
+        est, lct = (np.full_like(e[0], -1), np.full_like(l[0], -1)) if fill else (e[0].copy(), l[0].copy())
+    return U, first, est, lct, launches, count
+
+
+def _pack_destructive(rows, one_machine, upper, env):
+    bound, first, est, lct, launches, count = (np.asarray(x) for x in zip(*rows))
+    upper_of = None if upper is None else np.broadcast_to(np.asarray(upper, np.int64), bound.shape)
+    return DestructiveResult(lower_bound=bound.astype(np.int32), first_bound=first.astype(np.int32), one_machine=np.asarray(one_machine, np.int32),
+                             est=est.astype(np.int32), lct=lct.astype(np.int32), launches=launches.astype(np.int64),
+                             propagations=count.astype(np.int64),
+                             proved_optimal=np.zeros(bound.shape, bool) if upper_of is None else bound >= upper_of, env=env)
+
+
+def _destructive_args(what, instances, upper, rounds, span, passes):
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError(f"{what} takes instances (a name, a path, an Instance, or a list of them): call propagate on a "
+                                  "BatchedJssEnv for anything else")
+    names = [instances] if isinstance(instances, (str, os.PathLike, Instance)) else list(instances)
+    if len(names) < 1:
+        raise ValueError(f"{what}: need at least one instance")
+    if int(rounds) < 0 or int(span) < 1 or not 1 <= int(passes) <= _abi.PROPAGATE_MAX_PASSES:
+        raise ValueError(f"{what}: rounds >= 0, span >= 1, passes in [1, {_abi.PROPAGATE_MAX_PASSES}]")
+    uppers = [None] * len(names) if upper is None else [int(x) for x in np.broadcast_to(np.asarray(upper, np.int64), (len(names),))]
+    if any(x is not None and not 0 <= x <= _abi.PROPAGATE_MAX_TIME for x in uppers):
+        raise ValueError(f"{what}: upper must lie in [0, {_abi.PROPAGATE_MAX_TIME}]")
+    return names, uppers
+
+
+def destructive_bound(instances, upper=None, shave=True, rounds=8, span=64, passes=256, device=None, _backend=None):
+    """A destructive lower bound per instance (one, or a list of them), by constraint propagation on the device
+    (``BatchedJssEnv.propagate``, include/jss_propagate.h) on a batch of one env per instance, which is only read.  Defined by
+    public calls alone, per instance:
+
+    scan    from ``solve_machines()[0]``, the one-machine bound of the empty selection: one ``propagate`` launch takes ``span``
+            consecutive trial makespans as candidates; the first that is not refuted is ``first_bound``; the next span follows
+            where all are refuted.  No makespan at or above ``upper`` (an int, or one per instance) is tried: the bound never
+            exceeds it.
+    shave   at the bound U, with the windows of U's propagation as one shared table: a round is one launch with two candidates
+            per operation whose window holds more than one start -- "the start is at most mid" and "at least mid + 1", mid the
+            middle of its starts.  A refuted half is cut off the table; both halves of one operation refuted refute U.  After a
+            round that cut something the table is propagated again, one candidate without a hypothesis.  U refuted: the bound is
+            U + 1 (scanned on, one makespan a launch) and shaving starts anew there.  It ends with a round that cuts nothing,
+            after ``rounds`` rounds at one U, or at ``upper``.
+
+    Returns a ``DestructiveResult``."""
+    names, uppers = _destructive_args("destructive_bound", instances, upper, rounds, span, passes)
+    G = len(names)
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+    env = BatchedJssEnv(names[0], batch=1, **kw) if G == 1 else BatchedJssEnv(names, batch=G, table_of_env=np.arange(G), order="interleaved", **kw)
+    be = env.backend
+    env.reset()
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    one_machine = host(env.solve_machines()[0]).astype(np.int64)
+    const = host(env.env_const).reshape(-1, _abi.NC)
+    ops = np.asarray(env.packed.ops).reshape(-1, env.jmax, env.mmax)
+    rows = []
+    for g in range(G):
+        def prop(ubs, est=None, lct=None, hyp=None, g=g):
+            out = env.propagate(np.asarray(ubs, np.int32), parents=np.full(len(ubs), g, np.int32), est=est, lct=lct, hyp=hyp, passes=passes,
+                                windows=True)
+            return host(out[0]), host(out[2]), host(out[3])
+        dur = (ops[int(const[g, _abi.C_TABLE])] & 0xFFFF).astype(np.int64)
+        rows.append(_destructive_loop(prop, dur, int(one_machine[g]), uppers[g], shave, rounds, int(span)))
+    return _pack_destructive(rows, one_machine, upper, env)
+
+
+def destructive_reference(instances, upper=None, shave=True, rounds=8, span=64, passes=256):
+    """``destructive_bound``'s loop over the NumPy mirrors ``solve_reference`` and ``propagate_reference``; the instance tables
+    come from a batch on the host-core twin, which is only reset."""
+    from .env import CpuBackend
+    names, uppers = _destructive_args("destructive_reference", instances, upper, rounds, span, passes)
+    G = len(names)
+    kw = dict(_backend=CpuBackend(threads=1))
+    env = BatchedJssEnv(names[0], batch=1, **kw) if G == 1 else BatchedJssEnv(names, batch=G, table_of_env=np.arange(G), order="interleaved", **kw)
+    env.reset()
+    const = np.asarray(env.backend.numpy(env.env_const)).reshape(-1, _abi.NC)
+    ops = np.asarray(env.packed.ops).reshape(-1, env.jmax, env.mmax)
+    one_machine = solve_reference(const, ops)[1].astype(np.int64)
+    rows = []
+    for g in range(G):
+        def prop(ubs, est=None, lct=None, hyp=None, g=g):
+            out = propagate_reference(const, ops, np.asarray(ubs), parents=np.full(len(ubs), g), est=est, lct=lct, hyp=hyp, passes=passes)
+            return out[0], out[2], out[3]
+        dur = (ops[int(const[g, _abi.C_TABLE])] & 0xFFFF).astype(np.int64)
+        rows.append(_destructive_loop(prop, dur, int(one_machine[g]), uppers[g], shave, rounds, int(span)))
+    return _pack_destructive(rows, one_machine, upper, None)
+
+
+def _destructive_target(env, groups, walkers, span=64, passes=256):
+    """the scan's bound of ``destructive_bound`` for every group of ``walkers`` envs of ``env`` (the group's first env is
+    asked), one entry per env"""
+    be = env.backend
+    host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
+    firsts = (np.arange(groups) * walkers).astype(np.int32)
+    start = host(env.solve_machines(parents=firsts)[0]).astype(np.int64)
+    out = np.zeros(groups, np.int32)
+    for g in range(groups):
+        def prop(ubs, g=g):
+            res = env.propagate(np.asarray(ubs, np.int32), parents=np.full(len(ubs), firsts[g], np.int32), passes=passes, windows=True)
+            return host(res[0]), host(res[2]), host(res[3])
+        out[g] = _destructive_scan(prop, int(start[g]), None, span)[0]
+    return np.repeat(out, walkers)

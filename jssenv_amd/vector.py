@@ -144,6 +144,10 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
         raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
                                   "(search.bottleneck_search takes a list of instances)")
 
+    def propagate(self, *args, **kwargs):
+        raise NotImplementedError("JssVectorEnv does not propagate operation windows: call propagate on a BatchedJssEnv "
+                                  "(search.destructive_bound takes a list of instances)")
+
     def close(self, **kwargs):
         self.env.synchronize()
         self.closed = True
