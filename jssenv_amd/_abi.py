@@ -160,6 +160,12 @@ PROPAGATE_MAX_PASSES = 4096
 PROPAGATE_MAX_TIME = 0x3FFFFFFF
 PROPAGATE_FIXPOINT, PROPAGATE_REFUTED, PROPAGATE_BUDGET = 0, 1, 2
 
+# include/jss_onestep.h: the one-step rollout of the flagship class (its own version).  The HIP library exports it from a twelfth
+# library, libjss_onestep_hip.so; the twin has no counterpart (jss_rollout / jss_rollout_steps are the form on the host).
+ONESTEP_VERSION = 1
+ONESTEP_SYMBOLS = ("jss_onestep_version", "jss_onestep_rollout", "jss_onestep_rollout_steps")
+ONESTEP_MAX_GROUP = 32            # jmax, mmax of the class: a 16- or 32-lane group per env
+
 _p = C.c_void_p
 
 
@@ -525,3 +531,21 @@ def check(lib, rc: int, what: str):
     if rc != 0:
         msg = lib.jss_error_string(rc)
         raise RuntimeError(f"{what} failed: {rc} ({msg.decode() if msg else '?'})")
+
+
+def bind_onestep(lib):
+    """Attach the prototypes of include/jss_onestep.h; raises AttributeError naming the missing symbol."""
+    for name in ONESTEP_SYMBOLS:
+        if not hasattr(lib, name):
+            raise AttributeError(f"library does not export {name}")
+    D, S, O = C.POINTER(JssDesc), C.POINTER(JssState), C.POINTER(JssOut)
+    lib.jss_onestep_version.restype = C.c_int
+    lib.jss_onestep_version.argtypes = []
+    lib.jss_onestep_rollout.restype = C.c_int
+    lib.jss_onestep_rollout.argtypes = [D, S, O, C.c_int, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _p]
+    lib.jss_onestep_rollout_steps.restype = C.c_int
+    lib.jss_onestep_rollout_steps.argtypes = [D, S, O, C.c_int, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(_p)]
+    if lib.jss_onestep_version() != ONESTEP_VERSION:
+        raise RuntimeError(f"include/jss_onestep.h version {lib.jss_onestep_version()}, this package binds {ONESTEP_VERSION}")
+    return lib

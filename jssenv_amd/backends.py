@@ -55,6 +55,17 @@ class HipBackend:
         self._machine_lib = None
         self._carlier_lib = None
         self._propagate_lib = None
+        self._onestep_lib = None
+
+    @property
+    def onestep_lib(self):
+        """libjss_onestep_hip.so (include/jss_onestep.h), loaded on first use; a missing library is an error."""
+        if self._onestep_lib is None:
+            path = _abi.library_path("libjss_onestep_hip.so")
+            if not os.path.isfile(path):
+                raise RuntimeError(f"{path} is missing: build it (jssenv_amd.build.build_onestep_extension)")
+            self._onestep_lib = _abi.bind_onestep(C.CDLL(path))
+        return self._onestep_lib
 
     @property
     def beam_lib(self):

@@ -15,6 +15,8 @@
   tenth HIP library built the same way;
 * ``libjss_propagate_hip.so`` -- constraint propagation on operation windows (include/jss_propagate.h), an eleventh HIP library
   built the same way;
+* ``libjss_onestep_hip.so`` -- the one-step rollout of the flagship class with write-through stores (include/jss_onestep.h), a
+  twelfth HIP library built the same way;
 * ``libjss_cpu.so``  -- the host-core twin with the identical C ABI (g++, OpenMP).
 """
 import os
@@ -66,9 +68,13 @@ CARLIER_OUT = os.path.join(_HERE, "libjss_carlier_hip.so")
 _PROPAGATE = os.path.join(_ROOT, "include", "jss_propagate.h")   # ... and constraint propagation on operation windows (jss_propagate)
 PROPAGATE_SRC = os.path.join(_HERE, "csrc", "jss_propagate.hip") # (libjss_propagate_hip.so: a library of its own as well)
 PROPAGATE_OUT = os.path.join(_HERE, "libjss_propagate_hip.so")
+_ONESTEP = os.path.join(_ROOT, "include", "jss_onestep.h")       # ... and the flagship class's one-step rollout (jss_onestep_*)
+ONESTEP_SRC = os.path.join(_HERE, "csrc", "jss_onestep.hip")     # (libjss_onestep_hip.so: a library of its own as well)
+ONESTEP_OUT = os.path.join(_HERE, "libjss_onestep_hip.so")
 _OWN_LIBRARY = (os.path.basename(BEAM_SRC), os.path.basename(BOUND_SRC), os.path.basename(ORDER_SRC),
                 os.path.basename(TABU_SRC), os.path.basename(BLOCK_SRC), os.path.basename(RELINK_SRC),
-                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC), os.path.basename(CARLIER_SRC), os.path.basename(PROPAGATE_SRC))   # sources that libjss_hip.so does not include
+                os.path.basename(DECODE_SRC), os.path.basename(MACHINE_SRC), os.path.basename(CARLIER_SRC), os.path.basename(PROPAGATE_SRC),
+                os.path.basename(ONESTEP_SRC))   # sources that libjss_hip.so does not include
 _CHECKS = os.path.join(_HERE, "csrc", "jss_abi_checks.hpp")     # the argument checks both libraries share
 _ROWS = os.path.join(_HERE, "csrc", "jss_env_rows.hpp")         # ... and the table of an env's rows
 
@@ -98,6 +104,7 @@ def build_extension(force: bool = False, extra=(), out: str = OUT) -> str:
         build_machine_extension(force)
         build_carlier_extension(force)
         build_propagate_extension(force)
+        build_onestep_extension(force)
     if not force and _fresh(out, deps):
         return out
     subprocess.check_call([hipcc(), *FLAGS, *extra, SRC, "-o", out])
@@ -192,6 +199,18 @@ def build_propagate_extension(force: bool = False) -> str:
     subprocess.check_call([hipcc(), *FLAGS, PROPAGATE_SRC, "-o", tmp])
     os.replace(tmp, PROPAGATE_OUT)
     return PROPAGATE_OUT
+
+
+def build_onestep_extension(force: bool = False, extra=(), out: str = ONESTEP_OUT) -> str:
+    csrc = os.path.dirname(ONESTEP_SRC)
+    deps = [ONESTEP_SRC, _CHECKS, _ROWS, _ONESTEP, _HEADER, _SEARCH, _RULES, _KEYS] + \
+           [os.path.join(csrc, f) for f in ("jss_common.hpp", "jss_packed_env.hpp")]
+    if not force and _fresh(out, deps):
+        return out
+    tmp = out + f".tmp{os.getpid()}"
+    subprocess.check_call([hipcc(), *FLAGS, *extra, ONESTEP_SRC, "-o", tmp])
+    os.replace(tmp, out)
+    return out
 
 
 def build_cpu_twin(force: bool = False) -> str:

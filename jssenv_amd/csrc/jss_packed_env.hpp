@@ -45,6 +45,18 @@ __device__ __forceinline__ void st_out(void *base, unsigned byte_off, T v) {
     else st_off<T>(base, byte_off, v);
 }
 
+// a 16-byte state word (env header, compact job record): plain, or write-through (wt_store16)
+template <bool WT>
+__device__ __forceinline__ void st_out16(void *base, unsigned byte_off, int4 v) {
+    if (WT) {
+        float4 f;
+        f.x = as_float(v.x); f.y = as_float(v.y); f.z = as_float(v.z); f.w = as_float(v.w);
+        wt_store16(base, byte_off, f);
+    } else {
+        st_off(base, byte_off, v);
+    }
+}
+
 template <int G, int TAB>
 struct PCtx {                 // per-lane view of "my env"
     int lane, gl, gbase;      // gl = lane within the group, gbase = first lane of the group
@@ -878,16 +890,18 @@ enum { kStoreAll = 0, kStoreCompare = 1, kStoreCause = 2 };
 #ifndef JSS_ONE_STEP_STORES
 #define JSS_ONE_STEP_STORES kStoreCause      // (-DJSS_ONE_STEP_STORES=kStoreCompare: the A/B partner)
 #endif
-template <int G, int TAB, int DIFF = kStoreCompare>
+// WT: the env header and the compact record leave as write-through stores (the one-step kernels of jss_onestep.hip)
+template <int G, int TAB, int DIFF = kStoreCompare, bool WT = false>
 __device__ __forceinline__ void p_store(const PEnv<G> &e, const PCtx<G, TAB> &c, const Params &p, const PHeader &hd,
                                         const PRaw<G> &raw, bool fresh, bool moved = false, int a_sched = -1) {
+    static_assert(!WT || tab_compact(TAB), "write-through state stores: compact records only");
     if (!c.alive) return;
     const bool adv = DIFF == kStoreCause && moved;
     const unsigned jm = (unsigned)p.d.jmax, mm = (unsigned)p.d.mmax;
     const size_t fe = (size_t)c.first_env;
     const PRaw<G> now = p_pack(e, c, hd);
     if (c.gl == 0) {
-        st_off(p.s.env + fe * JSS_NH, c.rel * (JSS_NH * 4u), now.h);
+        st_out16<WT>(p.s.env + fe * JSS_NH, c.rel * (JSS_NH * 4u), now.h);
         if (fresh) {   // the instance constants of the env travel with it from here on (include/jss_hip.h JSS_C_*)
             const PNorm n = p_norm(c);
             int32_t *cp = p.s.env_const + fe * JSS_NC;
@@ -929,7 +943,7 @@ __device__ __forceinline__ void p_store(const PEnv<G> &e, const PCtx<G, TAB> &c,
             bool dirty;
             if (DIFF == kStoreCause) dirty = head_dirty || rest_dirty;
             else dirty = DIFF == kStoreAll || lo.x != raw.lo.x || lo.y != raw.lo.y || lo.z != raw.lo.z || lo.w != raw.lo.w;
-            if (fresh || dirty) st_off(p.s.job + fe * jm * JSS_NFC, (c.rel * jm + c.gl) * (JSS_NFC * 4u), lo);
+            if (fresh || dirty) st_out16<WT>(p.s.job + fe * jm * JSS_NFC, (c.rel * jm + c.gl) * (JSS_NFC * 4u), lo);
         }
     } else if (c.jvalid || (fresh && (unsigned)c.gl < jm)) {
         int32_t *jb = p.s.job + fe * jm * JSS_NF;
@@ -1090,7 +1104,8 @@ __device__ __forceinline__ bool p_step_call(PEnv<G> &e, PHeader &hd, PCtx<G, TAB
 }
 
 // (a_sched / restarted: what the one step of kStep / kRollout1 did to my env -- p_store, kStoreCause)
-template <int G, int MODE, int TAB>
+// WT: the rollout modes' reset fill, solution entry and reward / done / makespan leave as write-through stores (jss_onestep.hip)
+template <int G, int MODE, int TAB, bool WT = false>
 __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c, const Params &p, int a_in, bool selected,
                                        int32_t *mvtab, float *scratch, bool wave_whole, int &a_sched, bool &restarted, int cw = 0) {
     const size_t fe = (size_t)c.first_env;
@@ -1158,7 +1173,7 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
             const bool do_reset = c.alive && done0 && autoreset;
             const bool do_step = c.alive && !done0;
             if (MODE != kRollout1 && MODE != kTraj && __ballot(do_reset || do_step) == 0) break;  // every env frozen
-            p_reset(e, c, p, do_reset);
+            p_reset<G, TAB, WT>(e, c, p, do_reset);
             if (do_reset) {
                 hd.episode += 1;
                 hd.step = 0;
@@ -1170,7 +1185,7 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
                 a_sched = a;
                 restarted = do_reset;
             }
-            const int rn = p_step(e, c, p, a, mvtab);
+            const int rn = p_step<G, TAB, WT>(e, c, p, a, mvtab);
             const bool done1 = !grp_any<G>(e.legal, c.gbase);            // collective: outside the divergent branch
             if (do_step) {
                 last_rn = rn;
@@ -1195,9 +1210,9 @@ __device__ __forceinline__ bool p_body(PEnv<G> &e, PHeader &hd, PCtx<G, TAB> &c,
         if (p.s.counters) p_bump_counters(c, p, cw, n_steps, n_done, sum_makespan, sum_rn);
 #endif
         if (c.alive && c.gl == 0) {
-            if (n_steps) st_off<float>(p.o.reward + fe, c.rel * 4u, div_by((float)last_rn, (float)c.max_time_op, p_norm(c).r_op));
-            st_off<uint8_t>(p.o.done + fe, c.rel, done ? 1 : 0);
-            if (last_makespan >= 0) st_off<int>(p.o.makespan + fe, c.rel * 4u, last_makespan);
+            if (n_steps) st_out<WT, float>(p.o.reward + fe, c.rel * 4u, div_by((float)last_rn, (float)c.max_time_op, p_norm(c).r_op));
+            st_out<WT, uint8_t>(p.o.done + fe, c.rel, (uint8_t)(done ? 1 : 0));
+            if (last_makespan >= 0) st_out<WT, int>(p.o.makespan + fe, c.rel * 4u, last_makespan);
 #ifndef JSS_COUNTERS_PLAIN
             if (p.s.counters) add_counters(p.s.counters + (fe + c.rel) * 4, n_steps, n_done, sum_makespan, sum_rn);
 #endif
@@ -1273,9 +1288,12 @@ __device__ __forceinline__ void p_lookahead(PEnv<G> &e, PHeader &hd, const PCtx<
 #endif
 // One workgroup's share of a packed launch: `block` = its index among the workgroups of THIS env set (blockIdx.x of a
 // plain launch; a workgroup of the fused multi-set grid -- jss_multi_kernel -- passes its index within its own set).
-template <int G, int MODE, int TAB, bool PADDED = false>
+// WT: every store of the call -- state, solution, outputs, observation -- is a write-through store (jss_onestep.hip: the one-step
+// rollout on a shared table with compact records, the only instantiation with it).
+template <int G, int MODE, int TAB, bool PADDED = false, bool WT = false>
 __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t *lds) {
     static_assert(!PADDED || (MODE != kTraj && MODE != kSteps && MODE != kSession), "the recorders write whole rows");
+    static_assert(!WT || (MODE == kRollout1 && tab_compact(TAB) && !PADDED), "write-through stores: p_body's rollout branch, compact records");
     constexpr int E = kWave / G;                      // envs per wave
     constexpr int EB = E * kWavesPerBlock;            // envs per workgroup
     const int lane = threadIdx.x & (kWave - 1);
@@ -1398,19 +1416,19 @@ __device__ __forceinline__ void packed_block(const Params &p, int block, int32_t
     int a_sched;
     bool restarted;
 #ifdef JSS_COUNTERS_PLAIN
-    const bool fresh = p_body<G, MODE, TAB>(e, hd, c, p, a_in, selected, mvtab, scratch, wave_whole, a_sched, restarted, raw.cw);
+    const bool fresh = p_body<G, MODE, TAB, WT>(e, hd, c, p, a_in, selected, mvtab, scratch, wave_whole, a_sched, restarted, raw.cw);
 #else
-    const bool fresh = p_body<G, MODE, TAB>(e, hd, c, p, a_in, selected, mvtab, scratch, wave_whole, a_sched, restarted);
+    const bool fresh = p_body<G, MODE, TAB, WT>(e, hd, c, p, a_in, selected, mvtab, scratch, wave_whole, a_sched, restarted);
 #endif
     if (MODE == kPolicy) return;
     // (by cause with per-env tables only: +1.6 % on 15x15 x 65 536, full records 67 -> 61 VGPRs = 8 wavefronts per SIMD; on a
     //  shared table -- 16-byte records, four words to compare -- it measured 0..2 % SLOWER: profiles/r06_misc/stores_by_cause_ab.txt)
     constexpr int kDiffStores = (MODE == kRollout || MODE == kTraj || MODE == kSteps) ? kStoreAll
                                 : ((MODE == kStep || MODE == kLogits || MODE == kRollout1) && tab_global(TAB)) ? JSS_ONE_STEP_STORES : kStoreCompare;
-    p_store<G, TAB, kDiffStores>(e, c, p, hd, raw, fresh, restarted || e.t != raw.h.x, a_sched);
-    p_store_mask<G, TAB, false, PADDED>(e, c, p, p.o.action_mask + fe * (p.d.jmax + 1));
+    p_store<G, TAB, kDiffStores, WT>(e, c, p, hd, raw, fresh, restarted || e.t != raw.h.x, a_sched);
+    p_store_mask<G, TAB, WT, PADDED>(e, c, p, p.o.action_mask + fe * (p.d.jmax + 1));
     if (!JSS_ABLATED(p, JSS_ABLATE_OBS))
-        p_store_obs<G, TAB, false, PADDED>(e, c, p, p.o.real_obs + fe * p.d.jmax * 7, scratch, wave_whole);
+        p_store_obs<G, TAB, WT, PADDED>(e, c, p, p.o.real_obs + fe * p.d.jmax * 7, scratch, wave_whole);
 }
 
 template <int G, int MODE, int TAB>

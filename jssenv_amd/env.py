@@ -1868,6 +1868,21 @@ class BatchedJssEnv:
             info["entropy"] = self._lg_entropy
         return info
 
+    def _onestep_lib(self, kind_code):
+        """libjss_onestep_hip.so (include/jss_onestep.h) when this batch and the stock rule ``kind_code`` are in its class -- the
+        packed flavour on one shared instance with compact records --, else None: the call goes to jss_rollout /
+        jss_rollout_steps.  ``JSS_ONESTEP=0`` in the environment: always None (A/B runs, tests).  Same results either way."""
+        be = self.backend
+        in_class = self.__dict__.get("_onestep_class")
+        if in_class is None:                          # (the batch's side of it: fixed when the env is built)
+            d = self._desc
+            in_class = self._onestep_class = bool(
+                hasattr(be, "onestep_lib") and self._classes is None and d.n_tables == 1 and not d.table_of_env
+                and d.record_ints == _abi.NFC and not (d.kernel & 1) and max(d.jmax, d.mmax) <= _abi.ONESTEP_MAX_GROUP)
+        if not in_class or not 0 <= kind_code < (1 << 24) or os.environ.get("JSS_ONESTEP", "1") == "0":
+            return None
+        return be.onestep_lib
+
     def rollout(self, kind: Union[str, int] = "random", n_iter: int = 1, seed: Optional[int] = None,
                 autoreset: bool = True, explore: float = 0.0, weights=None, keys=None, nope_key=None):
         """n_iter x (policy + step) per env in ONE launch (state stays in registers).  ``kind="weighted"`` with
@@ -1889,7 +1904,11 @@ class BatchedJssEnv:
                 self._refuse_fresh("rollout(n_iter > 1, autoreset=True)")
             self.generate(self.done)      # one iteration: it restarts exactly the envs found done
         sd, q16 = self.seed if seed is None else int(seed), int(round(explore * 65536))
-        if not sel.stock or self._classes is None:    # (the caller's selectors on a batch by shape class: the padded extents' kernel)
+        one = self._onestep_lib(sel.arg) if sel.stock and n_iter == 1 else None
+        if one is not None:                           # the flagship class, one iteration: the kernel with write-through stores
+            with be.on_device():
+                _abi.check(be.lib, one.jss_onestep_rollout(d, s, o, sel.arg, sd, q16, 1, flags, be.stream()), "jss_onestep_rollout")
+        elif not sel.stock or self._classes is None:  # (the caller's selectors on a batch by shape class: the padded extents' kernel)
             with be.on_device():
                 sel.call(be.lib, "rollout", (d, s, o), sd, q16, n_iter, flags, be.stream())
         elif n_iter == 1:                             # by shape class: one grid over the classes
@@ -1927,11 +1946,13 @@ class BatchedJssEnv:
                                               flags | (_abi.ROLLOUT_FORK_JOIN if n > 1 and hasattr(be, "stream_array") else 0), n, streams)
                 _abi.check(be.lib, rc, "jss_multi_rollout")
                 return self._obs(), self.reward, self.done, False, {}
+            one = self._onestep_lib(k)
+            fn = be.lib.jss_rollout_steps if one is None else one.jss_onestep_rollout_steps
             if hasattr(be, "stream_array"):     # the library forks / joins the side streams itself (two C calls per stream)
-                rc = be.lib.jss_rollout_steps(d, s, o, k, sd, int(round(explore * 65536)), int(steps),
-                                              flags | _abi.ROLLOUT_FORK_JOIN, int(n_sub), be.stream_array(int(n_sub)))
+                rc = fn(d, s, o, k, sd, int(round(explore * 65536)), int(steps),
+                        flags | _abi.ROLLOUT_FORK_JOIN, int(n_sub), be.stream_array(int(n_sub)))
             else:
-                rc = be.with_streams(int(n_sub), lambda streams: be.lib.jss_rollout_steps(
+                rc = be.with_streams(int(n_sub), lambda streams: fn(
                     d, s, o, k, sd, int(round(explore * 65536)), int(steps), flags, int(n_sub), streams), self._stream_events)
         _abi.check(be.lib, rc, "jss_rollout_steps")
         return self._obs(), self.reward, self.done, False, {}
@@ -1984,7 +2005,9 @@ class BatchedJssEnv:
         d, s, o = self._refs()
         with be.on_device():
             streams = be.stream_array(int(n_sub))
-        fn, sd, q16, n_steps, n = be.lib.jss_rollout_steps, self.seed if seed is None else int(seed), int(round(explore * 65536)), int(steps), int(n_sub)
+        one = self._onestep_lib(k)
+        fn = be.lib.jss_rollout_steps if one is None else one.jss_onestep_rollout_steps
+        sd, q16, n_steps, n = self.seed if seed is None else int(seed), int(round(explore * 65536)), int(steps), int(n_sub)
         lib = be.lib
         if self._classes is not None:
             n = min(n, 4)
