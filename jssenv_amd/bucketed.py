@@ -33,6 +33,7 @@ import numpy as np
 from . import _abi
 from .env import BatchedJssEnv, stock_code
 from .instances import resolve_instance
+from .search_calls import refuses_search_calls
 
 
 def shape_class(jobs: int, machines: int) -> int:
@@ -43,6 +44,7 @@ def shape_class(jobs: int, machines: int) -> int:
     return 2 if jobs <= 64 else 3
 
 
+@refuses_search_calls
 class BucketedJssEnv:
     def __init__(self, instances: Sequence, batch: Optional[int] = None, device=None, seed: int = 0,
                  env_id_base: int = 0, launch: str = "grid", _backend=None):
@@ -209,54 +211,6 @@ class BucketedJssEnv:
         for (_, b), a in zip(each, args):
             b._logits_keep = a[3]                    # alive until the launch has read it
         return {k: (b._obs(), b.reward, b.done, False, b._logits_info(logp, entropy)) for k, b in each}
-
-    def evaluate_order(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
-                                  "(search.improve takes one, or a list of instances)")
-
-    def tabu(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu on a BatchedJssEnv "
-                                  "(search.tabu_search takes a list of instances)")
-
-    def tabu_blocks(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
-                                  "(search.tabu_search takes a list of instances)")
-
-    def relink(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not relink machine orders: call relink on a BatchedJssEnv "
-                                  "(search.relink_search takes a list of instances)")
-
-    def order_distance(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
-                                  "(search.relink_search takes a list of instances)")
-
-    def decode_keys(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not decode key tables: call decode_keys on a BatchedJssEnv "
-                                  "(search.brkga_search takes a list of instances)")
-
-    def evolve_keys(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
-                                  "(search.brkga_search takes a list of instances)")
-
-    def relax_machines(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not relax partial selections: call relax_machines on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def bottleneck(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def solve_machines(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not solve one-machine problems: call solve_machines on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def bottleneck_exact(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def propagate(self, *args, **kwargs):
-        raise NotImplementedError("BucketedJssEnv does not propagate operation windows: call propagate on a BatchedJssEnv "
-                                  "(search.destructive_bound takes a list of instances)")
 
     def synchronize(self):
         for _, b in self._each():

@@ -326,16 +326,12 @@ class JssEnv(gymnasium_base("Env")):
         the two flat operation indices ``swap=(a, b)`` exchanged first; -1 refused, -2 cyclic.  ``start`` / ``tail`` / ``pairs``
         add the host arrays of the one row: ``(makespan[, start][, tail][, pair_a, pair_b, n_pairs])``."""
         b = self._b
-        if rank is not None:
-            r = np.full((1, b.jmax, b.mmax), -1, np.int32)
-            rank = np.asarray(rank)
-            r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
-            rank = r
+        rank = None if rank is None else self._order_row(rank)
         swaps = None if swap is None else ([int(swap[0])], [int(swap[1])])
         out = b.evaluate_order(rank, None, swaps, start, tail, pairs)
         if not isinstance(out, tuple):
             return int(b.backend.numpy(out)[0])
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return (int(host[0]),) + tuple(int(x) if x.ndim == 0 else x for x in host[1:])
 
     def tabu(self, rank=None, iters: int = 100, tenure: int = 8, target=None, trace: bool = False, last: bool = False):
@@ -343,13 +339,9 @@ class JssEnv(gymnasium_base("Env")):
         machine order ``rank`` (J x M or jmax x mmax; None: this env's finished ``solution``).  Returns
         ``(best_makespan, best_rank, info[, trace][, last_rank])``: an int (-1 refused, -2 cyclic) and host arrays."""
         b = self._b
-        if rank is not None:
-            r = np.full((1, b.jmax, b.mmax), -1, np.int32)
-            rank = np.asarray(rank)
-            r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
-            rank = r
+        rank = None if rank is None else self._order_row(rank)
         out = b.tabu(rank, iters, int(tenure), None if target is None else int(target), trace, last)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return (int(host[0]),) + tuple(host[1:])
 
     def tabu_blocks(self, rank=None, iters: int = 100, tenure: int = 8, target=None, reach: int = 0, trace: bool = False,
@@ -358,21 +350,22 @@ class JssEnv(gymnasium_base("Env")):
         ``iters`` moves from the machine order ``rank`` (J x M or jmax x mmax; None: this env's finished ``solution``).  Returns
         ``(best_makespan, best_rank, info[, trace][, last_rank][, move_log])``: an int (-1 refused, -2 cyclic) and host arrays."""
         b = self._b
-        if rank is not None:
-            r = np.full((1, b.jmax, b.mmax), -1, np.int32)
-            rank = np.asarray(rank)
-            r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
-            rank = r
+        rank = None if rank is None else self._order_row(rank)
         out = b.tabu_blocks(rank, iters, int(tenure), None if target is None else int(target), reach, trace, last, log)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return (int(host[0]),) + tuple(host[1:])
 
-    def _order_row(self, rank):
+    def _order_row(self, rank, fill=-1):
+        """a J x M or jmax x mmax table as the (1, jmax, mmax) int32 rank of the batch of one, ``fill`` in the padding"""
         b = self._b
-        r = np.full((1, b.jmax, b.mmax), -1, np.int32)
+        r = np.full((1, b.jmax, b.mmax), fill, np.int32)
         rank = np.asarray(rank)
         r[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
         return r
+
+    def _host_rows(self, out):
+        """row 0 of every array a call on the batch of one returned, on the host (None stays None)"""
+        return [None if x is None else np.asarray(self._b.backend.numpy(x))[0] for x in out]
 
     def relink(self, rank, guide, steps=None, until: int = 0, margin: int = 0, trace: bool = False, last: bool = True,
                log: bool = False):
@@ -382,7 +375,7 @@ class JssEnv(gymnasium_base("Env")):
         b = self._b
         out = b.relink(None if rank is None else self._order_row(rank), self._order_row(guide), steps, int(until), margin, trace,
                        last, log)
-        host = [None if x is None else np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return tuple(int(x) if k in (0, 2) and x is not None else x for k, x in enumerate(host))
 
     def order_distance(self, rank, guide) -> int:
@@ -402,16 +395,12 @@ class JssEnv(gymnasium_base("Env")):
         k[:keys.shape[-2], :keys.shape[-1]] = keys.reshape(keys.shape[-2:])
         out = b.decode_keys(k, None, float(delta), start, info)
         out = out if isinstance(out, tuple) else (out,)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return int(host[0]) if len(host) == 1 else (int(host[0]),) + tuple(host[1:])
 
     def _machine_row(self, rank):
-        """a J x M or jmax x mmax table as the (1, jmax, mmax) int32 rank of the batch of one"""
-        b = self._b
-        row = np.zeros((1, b.jmax, b.mmax), np.int32)
-        rank = np.asarray(rank)
-        row[0, :rank.shape[-2], :rank.shape[-1]] = rank.reshape(rank.shape[-2:])
-        return row
+        """``_order_row`` with 0 in the padding, as the one-machine calls and ``propagate`` take their tables"""
+        return self._order_row(rank, 0)
 
     def relax_machines(self, rank=None, fixed: int = 0, jps: bool = False, schrage: bool = False, head: bool = False, tail: bool = False,
                        rank_out: bool = False):
@@ -421,7 +410,7 @@ class JssEnv(gymnasium_base("Env")):
         ``head``, ``tail`` and ``rank_out`` (jmax, mmax), host arrays."""
         b = self._b
         out = b.relax_machines(None if rank is None else self._machine_row(rank), int(fixed), None, jps, schrage, head, tail, rank_out)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return tuple(int(x) for x in host[:3]) + tuple(host[3:])
 
     def bottleneck(self, bias=None, reopt: int = 1, rank=None, fixed=None, order: bool = False):
@@ -431,7 +420,7 @@ class JssEnv(gymnasium_base("Env")):
         b = self._b
         out = b.bottleneck(None, None if bias is None else np.asarray(bias, np.int32).reshape(1, -1), reopt,
                            None if rank is None else self._machine_row(rank), None if fixed is None else int(fixed), order)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return (int(host[0]),) + tuple(host[1:])
 
     def solve_machines(self, rank=None, fixed: int = 0, nodes: int = 256, opt: bool = False, low: bool = False, nodes_used: bool = False,
@@ -443,7 +432,7 @@ class JssEnv(gymnasium_base("Env")):
         b = self._b
         out = b.solve_machines(None if rank is None else self._machine_row(rank), int(fixed), None, nodes, opt, low, nodes_used, proved,
                                head, tail, rank_out)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         at = 3 + int(opt) + int(low) + int(nodes_used)
         if proved:
             host[at] = int(host[at]) & (2 ** 64 - 1)
@@ -456,7 +445,7 @@ class JssEnv(gymnasium_base("Env")):
         b = self._b
         out = b.bottleneck_exact(None, None if bias is None else np.asarray(bias, np.int32).reshape(1, -1), reopt, nodes,
                                  None if rank is None else self._machine_row(rank), None if fixed is None else int(fixed), order)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return (int(host[0]),) + tuple(host[1:])
 
     def propagate(self, ub, rank=None, fixed: int = 0, est=None, lct=None, hyp=None, passes: int = 256, windows: bool = False):
@@ -469,7 +458,7 @@ class JssEnv(gymnasium_base("Env")):
         out = b.propagate(int(ub), None if rank is None else self._machine_row(rank), int(fixed), None,
                           None if est is None else self._machine_row(est), None if lct is None else self._machine_row(lct),
                           None if hyp is None else tuple(np.asarray([int(x)], np.int32) for x in hyp), passes, windows)
-        host = [np.asarray(b.backend.numpy(x))[0] for x in out]
+        host = self._host_rows(out)
         return tuple(int(x) for x in host[:2]) + tuple(host[2:])
 
     def render(self, mode: str = "human"):

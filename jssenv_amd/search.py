@@ -57,8 +57,71 @@ import numpy as np
 from . import _abi
 from .env import BatchedJssEnv
 from .instances import Instance, PackedBatch
+from .search_calls import library
 
 SKIP = _abi.ACTION_SKIP
+
+
+# ---- the library of a family on a backend (search_calls.library), by the names the case modules of the tests call -----------
+def beam_library(backend): return library(backend, "beam")                # noqa: E704
+def bound_library(backend): return library(backend, "bound")              # noqa: E704
+def order_library(backend): return library(backend, "order")              # noqa: E704
+def tabu_library(backend): return library(backend, "tabu")                # noqa: E704
+def block_library(backend): return library(backend, "block")              # noqa: E704
+def relink_library(backend): return library(backend, "relink")            # noqa: E704
+def decode_library(backend): return library(backend, "decode")            # noqa: E704
+def machine_library(backend): return library(backend, "machine")          # noqa: E704
+def carlier_library(backend): return library(backend, "carlier")          # noqa: E704
+def propagate_library(backend): return library(backend, "propagate")      # noqa: E704
+
+
+# ---- what the drivers share: the instances, the batch of groups, the target, the winners ----------------------------------------
+_TARGETS = ("lower_bound", "one_machine", "one_machine_exact", "destructive")
+
+
+def _instance_groups(what, instances, hint):
+    """``names, G``: the instances of a driver as a list and their number; NotImplementedError for an env object, with ``hint``,
+    the call that serves it instead"""
+    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
+        raise NotImplementedError(f"{what} takes instances (a name, a path, an Instance, or a list of them): {hint}")
+    names = [instances] if isinstance(instances, (str, os.PathLike, Instance)) else list(instances)
+    if len(names) < 1:
+        raise ValueError(f"{what}: need at least one instance")
+    return names, len(names)
+
+
+def _grouped_env(names, per_group, seed, device, _backend):
+    """one batch of ``len(names)`` groups of ``per_group`` envs each, group g on instance g"""
+    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
+    if len(names) == 1:
+        return BatchedJssEnv(names[0], batch=per_group, seed=int(seed or 0), **kw)
+    return BatchedJssEnv(names, batch=len(names) * per_group, table_of_env=np.repeat(np.arange(len(names)), per_group),
+                         order="interleaved", seed=int(seed or 0), **kw)
+
+
+def _check_target(what, target):
+    if isinstance(target, str) and target not in _TARGETS:
+        raise ValueError(f"{what}: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
+
+
+def _resolve_target(what, env, target, G, per_group):
+    """The target of every env of the (reset) batch ``env``: a bound by its name, as the batch's backend returns it; None; or an
+    int, or one per instance, repeated over the groups' envs on the host."""
+    _check_target(what, target)
+    if isinstance(target, str):
+        return (env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
+                else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, per_group))
+    if target is None:
+        return None
+    return np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), per_group)
+
+
+def _group_winners(mk, G, W):
+    """``walker, winner``: of every group of W the walker with the lowest ``(makespan, walker)`` -- one without a schedule counts
+    as +inf --, within its group and within the batch"""
+    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
+    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
+    return walker, (np.arange(G) * W + walker).astype(np.int32)
 
 
 # ---- the selection, in NumPy -------------------------------------------------------------------------------------------
@@ -117,18 +180,6 @@ def beam_select_reference(cand_parent, makespan, steps, reward_num, done, env_ma
 
 
 # ---- the entry point -----------------------------------------------------------------------------------------------------
-def beam_library(backend):
-    """The library of ``backend`` that exports include/jss_beam.h: ``backend.beam_lib`` (HipBackend: libjss_beam_hip.so, loaded
-    on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
-    lib = getattr(backend, "beam_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not hasattr(lib, "jss_beam_select"):
-            raise RuntimeError("beam search: the backend's library does not export jss_beam_select (include/jss_beam.h)")
-        _abi.bind_beam(lib)
-    return lib
-
-
 def _select_call(be, lib, G, W, A, dedupe, cand_parent, makespan, steps, reward_num, done, env_makespan, src, action, score,
                  next_parent, counts):
     p = be.ptr
@@ -174,18 +225,6 @@ def lookahead_into(env, sel, cand_parent, actions, makespan, steps, reward_num, 
 
 
 # ---- makespan lower bounds (include/jss_bound.h), in NumPy ----------------------------------------------------------------
-def bound_library(backend):
-    """The library of ``backend`` that exports include/jss_bound.h: ``backend.bound_lib`` (HipBackend: libjss_bound_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
-    lib = getattr(backend, "bound_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not hasattr(lib, "jss_bound"):
-            raise RuntimeError("lower_bound: the backend's library does not export jss_bound (include/jss_bound.h)")
-        _abi.bind_bound(lib)
-    return lib
-
-
 def lower_bound_reference(env_header, env_const, solution, ops, rem, parents=None, actions=None, mask=None, est_fill=None,
                           block=256):
     """include/jss_bound.h's semantics on host arrays, written from the header's definition (all candidates of a block at once,
@@ -280,18 +319,6 @@ def lower_bound_reference(env_header, env_const, solution, ops, rem, parents=Non
 
 
 # ---- machine orders (include/jss_order.h), in NumPy ---------------------------------------------------------------------------
-def order_library(backend):
-    """The library of ``backend`` that exports include/jss_order.h: ``backend.order_lib`` (HipBackend: libjss_order_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
-    lib = getattr(backend, "order_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.ORDER_SYMBOLS):
-            raise RuntimeError("evaluate_order: the backend's library does not export include/jss_order.h")
-        _abi.bind_order(lib)
-    return lib
-
-
 def order_eval_reference(env_const, ops, rank, parents=None, swap_a=None, swap_b=None, pair_cap=None, fill=-1):
     """include/jss_order.h's jss_order_eval on host arrays, written from the header's definition, one candidate after the
     other: the machines' orders by a lexicographic sort, the starts over the operations in an order in which every predecessor
@@ -440,11 +467,7 @@ def beam_search(instances, kind="SPT", width=64, device=None, dedupe=True, seed=
     if G < 1:
         raise ValueError("beam_search: need at least one instance")
     S = G * W
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-    if G == 1:
-        a = BatchedJssEnv(names[0], batch=S, seed=int(seed or 0), **kw)
-    else:
-        a = BatchedJssEnv(names, batch=S, table_of_env=np.repeat(np.arange(G), W), order="interleaved", seed=int(seed or 0), **kw)
+    a = _grouped_env(names, W, seed, device, _backend)
     be, A = a.backend, a.jmax + 1
     if W * A > 65536:
         raise ValueError(f"beam_search: width * (jmax + 1) = {W * A} exceeds 65536 (include/jss_beam.h)")
@@ -557,11 +580,7 @@ def improve(env_or_instances, kind="SPT", max_iter=None, pair_cap=128, check_eve
         names = [env_or_instances] if one else list(env_or_instances)
         if not names:
             raise ValueError("improve: need at least one instance")
-        kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-        if len(names) == 1:
-            env = BatchedJssEnv(names[0], batch=1, **kw)
-        else:
-            env = BatchedJssEnv(names, batch=len(names), table_of_env=np.arange(len(names)), order="interleaved", **kw)
+        env = _grouped_env(names, 1, 0, device, _backend)
         fresh = True
     be = env.backend
     if fresh:
@@ -613,18 +632,6 @@ def improve(env_or_instances, kind="SPT", max_iter=None, pair_cap=128, check_eve
 
 
 # ---- tabu search over swaps of adjacent critical operations (include/jss_tabu.h) ---------------------------------------------------
-def tabu_library(backend):
-    """The library of ``backend`` that exports include/jss_tabu.h: ``backend.tabu_lib`` (HipBackend: libjss_tabu_hip.so, loaded
-    on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
-    lib = getattr(backend, "tabu_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.TABU_SYMBOLS):
-            raise RuntimeError("tabu: the backend's library does not export include/jss_tabu.h")
-        _abi.bind_tabu(lib)
-    return lib
-
-
 def tabu_reference(env_const, ops, rank, iters, tenure, target=None, fill=-1, log=None):
     """include/jss_tabu.h's jss_tabu_search on host arrays, written from the header's definition on top of
     ``order_eval_reference``, one walker after the other: the start's refusal, cycle and order, every move's pairs and every
@@ -707,18 +714,6 @@ def tabu_reference(env_const, ops, rank, iters, tenure, target=None, fill=-1, lo
 
 
 # ---- tabu search over block insertions, scored by heads and tails (include/jss_block.h) -----------------------------------------
-def block_library(backend):
-    """The library of ``backend`` that exports include/jss_block.h: ``backend.block_lib`` (HipBackend: libjss_block_hip.so, loaded
-    on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
-    lib = getattr(backend, "block_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.BLOCK_SYMBOLS):
-            raise RuntimeError("tabu_blocks: the backend's library does not export include/jss_block.h")
-        _abi.bind_block(lib)
-    return lib
-
-
 def block_reference(env_const, ops, rank, iters, tenure, target=None, reach=0, fill=-1, log=None):
     """include/jss_block.h's jss_block_search on host arrays, written from the header's definition on top of
     ``order_eval_reference``, one walker after the other: the start's refusal, cycle and order, every move's starts and tails and
@@ -872,18 +867,6 @@ def block_reference(env_const, ops, rank, iters, tenure, target=None, reach=0, f
 
 
 # ---- path relinking between machine orders (include/jss_relink.h) ----------------------------------------------------------------
-def relink_library(backend):
-    """The library of ``backend`` that exports include/jss_relink.h: ``backend.relink_lib`` (HipBackend: libjss_relink_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbol."""
-    lib = getattr(backend, "relink_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.RELINK_SYMBOLS):
-            raise RuntimeError("relink: the backend's library does not export include/jss_relink.h")
-        _abi.bind_relink(lib)
-    return lib
-
-
 def relink_reference(env_const, ops, rank, guide, steps, until, margin=0, fill=-1, log=None):
     """include/jss_relink.h's jss_relink_walk on host arrays, written from the header's definition on top of
     ``order_eval_reference``, one walker after the other: the refusal and the cycle check of both rows, every move's starts and
@@ -1059,34 +1042,15 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     reach = int(reach)
     if not 0 <= reach <= _abi.BLOCK_MAX_REACH or (reach and moves == "swap"):
         raise ValueError(f"tabu_search: reach must lie in [0, {_abi.BLOCK_MAX_REACH}], and is 0 with moves='swap'")
-    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
-        raise NotImplementedError("tabu_search takes instances (a name, a path, an Instance, or a list of them): call tabu on a "
-                                  "BatchedJssEnv for anything else")
-    one = isinstance(instances, (str, os.PathLike, Instance))
-    names = [instances] if one else list(instances)
-    G = len(names)
-    if G < 1:
-        raise ValueError("tabu_search: need at least one instance")
+    names, G = _instance_groups("tabu_search", instances, "call tabu on a BatchedJssEnv for anything else")
     lo, hi = (int(tenure), int(tenure)) if np.ndim(tenure) == 0 else (int(tenure[0]), int(tenure[1]))
     if not 0 <= lo <= hi <= _abi.TABU_MAX_TENURE:
         raise ValueError(f"tabu_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}], low <= high")
     S = G * W
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-    if G == 1:
-        env = BatchedJssEnv(names[0], batch=S, seed=int(seed or 0), **kw)
-    else:
-        env = BatchedJssEnv(names, batch=S, table_of_env=np.repeat(np.arange(G), W), order="interleaved", seed=int(seed or 0), **kw)
+    env = _grouped_env(names, W, seed, device, _backend)
     be = env.backend
     env.reset()
-    if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
-            raise ValueError("tabu_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
-        tgt = (env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
-               else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, W))
-    elif target is None:
-        tgt = None
-    else:
-        tgt = np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), W)
+    tgt = _resolve_target("tabu_search", env, target, G, W)
     env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False, explore=explore, seed=seed)
     ten = (lo + (np.arange(S) % W) % (hi - lo + 1)).astype(np.int32)
     if moves == "block":
@@ -1096,10 +1060,7 @@ def tabu_search(instances, kind="SPT", walkers=64, iters=1000, tenure=(5, 12), e
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     mk, info = host(best).astype(np.int32), host(info).astype(np.int32)
     tgt = None if tgt is None else host(tgt).astype(np.int32)
-    # the lowest (best_makespan, walker) of every group; a walker without a schedule counts as +inf
-    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
-    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
-    winner = (np.arange(G) * W + walker).astype(np.int32)
+    walker, winner = _group_winners(mk, G, W)
     again, start = env.evaluate_order(best_rank, winner, start=True)
     assert np.array_equal(host(again), mk[winner])
     proven = info[:, 0] == 1
@@ -1146,34 +1107,15 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
         raise ValueError("relink_search: share is (a, b) with 0 <= a <= b and b >= 1")
     if not 0 <= reach <= _abi.BLOCK_MAX_REACH:
         raise ValueError(f"relink_search: reach must lie in [0, {_abi.BLOCK_MAX_REACH}]")
-    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
-        raise NotImplementedError("relink_search takes instances (a name, a path, an Instance, or a list of them): call relink and "
-                                  "tabu_blocks on a BatchedJssEnv for anything else")
-    one = isinstance(instances, (str, os.PathLike, Instance))
-    names = [instances] if one else list(instances)
-    G = len(names)
-    if G < 1:
-        raise ValueError("relink_search: need at least one instance")
+    names, G = _instance_groups("relink_search", instances, "call relink and tabu_blocks on a BatchedJssEnv for anything else")
     lo, hi = (int(tenure), int(tenure)) if np.ndim(tenure) == 0 else (int(tenure[0]), int(tenure[1]))
     if not 0 <= lo <= hi <= _abi.TABU_MAX_TENURE:
         raise ValueError(f"relink_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}], low <= high")
     S = G * W
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-    if G == 1:
-        env = BatchedJssEnv(names[0], batch=S, seed=int(seed or 0), **kw)
-    else:
-        env = BatchedJssEnv(names, batch=S, table_of_env=np.repeat(np.arange(G), W), order="interleaved", seed=int(seed or 0), **kw)
+    env = _grouped_env(names, W, seed, device, _backend)
     be = env.backend
     env.reset()
-    if isinstance(target, str):
-        if target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
-            raise ValueError("relink_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
-        tgt = (env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
-               else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, W))
-    elif target is None:
-        tgt = None
-    else:
-        tgt = np.repeat(np.broadcast_to(np.asarray(target, np.int32), (G,)), W)
+    tgt = _resolve_target("relink_search", env, target, G, W)
     env.rollout(kind, n_iter=3 * env.jmax * env.mmax, autoreset=False, explore=explore, seed=seed)
     ten = (lo + (np.arange(S) % W) % (hi - lo + 1)).astype(np.int32)
     best, best_rank, info = env.tabu_blocks(None, iters, ten, tgt, reach)
@@ -1208,9 +1150,7 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
     mk, info = host(best).astype(np.int32), host(info).astype(np.int32)
     tgt = None if tgt is None else host(tgt).astype(np.int32)
-    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
-    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
-    winner = (np.arange(G) * W + walker).astype(np.int32)
+    walker, winner = _group_winners(mk, G, W)
     again, start = env.evaluate_order(best_rank, winner, start=True)
     assert np.array_equal(host(again), mk[winner])
     proven = info[:, 0] == 1
@@ -1224,18 +1164,6 @@ def relink_search(instances, kind="SPT", walkers=64, iters=1000, rounds=4, share
 
 
 # ---- Giffler-Thompson decoding of key tables, one BRKGA generation (include/jss_decode.h) ------------------------------------------
-def decode_library(backend):
-    """The library of ``backend`` that exports include/jss_decode.h: ``backend.decode_lib`` (HipBackend: libjss_decode_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
-    lib = getattr(backend, "decode_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.DECODE_SYMBOLS):
-            raise RuntimeError("decode: the backend's library does not export include/jss_decode.h")
-        _abi.bind_decode(lib)
-    return lib
-
-
 def decode_reference(env_const, ops, keys, parents=None, delta=65536, fill=-1):
     """include/jss_decode.h's jss_decode_keys on host arrays, written from the header's definition, one candidate after the
     other.  ``keys`` (jmax, mmax), one table for all, or (n, jmax, mmax); ``parents`` (n,) or None (candidate c is env c);
@@ -1397,39 +1325,18 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
         raise ValueError("brkga_search: elite + mutants must not exceed the population")
     if not 0 <= int(tenure) <= _abi.TABU_MAX_TENURE:
         raise ValueError(f"brkga_search: tenure must lie in [0, {_abi.TABU_MAX_TENURE}]")
-    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
-        raise NotImplementedError("brkga_search takes instances (a name, a path, an Instance, or a list of them): call decode_keys "
-                                  "and evolve_keys on a BatchedJssEnv for anything else")
-    one = isinstance(instances, (str, os.PathLike, Instance))
-    names = [instances] if one else list(instances)
-    G = len(names)
-    if G < 1:
-        raise ValueError("brkga_search: need at least one instance")
+    names, G = _instance_groups("brkga_search", instances, "call decode_keys and evolve_keys on a BatchedJssEnv for anything else")
     rules = tuple(seed_rules or ())
     if len(rules) > P:
         raise ValueError("brkga_search: more seed rules than individuals")
-    if isinstance(target, str) and target not in ("lower_bound", "one_machine", "one_machine_exact", "destructive"):
-        raise ValueError("brkga_search: target is 'lower_bound', 'one_machine', 'one_machine_exact', 'destructive', None, an int or one int per instance")
+    _check_target("brkga_search", target)
     S = G * P
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-
-    def batch(per_group):
-        if G == 1:
-            return BatchedJssEnv(names[0], batch=per_group, seed=int(seed or 0), **kw)
-        return BatchedJssEnv(names, batch=G * per_group, table_of_env=np.repeat(np.arange(G), per_group), order="interleaved",
-                             seed=int(seed or 0), **kw)
-
-    env = batch(1)
+    env = _grouped_env(names, 1, seed, device, _backend)
     be = env.backend
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
-    if isinstance(target, str):
-        tgt = host(env.lower_bound() if target == "lower_bound" else env.relax_machines()[0] if target == "one_machine"
-                   else env.solve_machines()[0] if target == "one_machine_exact" else _destructive_target(env, G, 1)).astype(np.int32)
-    elif target is None:
-        tgt = None
-    else:
-        tgt = np.broadcast_to(np.asarray(target, np.int32), (G,)).copy()
+    tgt = _resolve_target("brkga_search", env, target, G, 1)
+    tgt = None if tgt is None else host(tgt).astype(np.int32)
     jmax, mmax = env.jmax, env.mmax
     xp = be.torch if getattr(be, "torch", None) is not None else np
     never = 2 ** 31 - 1
@@ -1463,12 +1370,11 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
         fitness, start = env.decode_keys(keys, parents, delta, start=True)
     mk = host(fitness).astype(np.int32)
     if polish:
-        walkers = batch(P)
+        walkers = _grouped_env(names, P, seed, device, _backend)
         walkers.reset()
         best, rank, _ = walkers.tabu_blocks(start, polish, int(tenure))
         mk = host(best).astype(np.int32)
-    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, P)
-    winner = (np.arange(G) * P + by_group.argmin(axis=1)).astype(np.int32)   # (the first of equal makespans)
+    _, winner = _group_winners(mk, G, P)
     if polish:
         again, begin = walkers.evaluate_order(rank, winner, start=True)
         assert np.array_equal(host(again), mk[winner])
@@ -1482,18 +1388,6 @@ def brkga_search(instances, population=256, generations=100, elite=0.15, mutants
 
 
 # ---- one-machine relaxations of partial selections, the shifting bottleneck construction (include/jss_machine.h) ----------------
-def machine_library(backend):
-    """The library of ``backend`` that exports include/jss_machine.h: ``backend.machine_lib`` (HipBackend: libjss_machine_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
-    lib = getattr(backend, "machine_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.MACHINE_SYMBOLS):
-            raise RuntimeError("relax_machines: the backend's library does not export include/jss_machine.h")
-        _abi.bind_machine(lib)
-    return lib
-
-
 def _jackson_preemptive(r, p, q):
     """the value of Jackson's preemptive schedule: always the released unfinished operation with the largest q"""
     n = len(r)
@@ -1711,23 +1605,8 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     if isinstance(target, str) and target not in ("lower_bound", "one_machine", "destructive") + (("one_machine_exact",) if nodes else ()):
         raise ValueError("bottleneck_search: target is 'one_machine', 'lower_bound', 'destructive', None, an int or one int per instance"
                          " ('one_machine_exact' with nodes > 0)")
-    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
-        raise NotImplementedError("bottleneck_search takes instances (a name, a path, an Instance, or a list of them): call "
-                                  "bottleneck on a BatchedJssEnv for anything else")
-    one = isinstance(instances, (str, os.PathLike, Instance))
-    names = [instances] if one else list(instances)
-    G = len(names)
-    if G < 1:
-        raise ValueError("bottleneck_search: need at least one instance")
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-
-    def batch(per_group):
-        if G == 1:
-            return BatchedJssEnv(names[0], batch=per_group, seed=int(seed or 0), **kw)
-        return BatchedJssEnv(names, batch=G * per_group, table_of_env=np.repeat(np.arange(G), per_group), order="interleaved",
-                             seed=int(seed or 0), **kw)
-
-    env = batch(1)
+    names, G = _instance_groups("bottleneck_search", instances, "call bottleneck on a BatchedJssEnv for anything else")
+    env = _grouped_env(names, 1, seed, device, _backend)
     be = env.backend
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
@@ -1745,13 +1624,11 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
     best, rank, info = env.bottleneck_exact(parents, bias, reopt, nodes) if nodes else env.bottleneck(parents, bias, reopt)
     info = host(info).astype(np.int32)
     if polish:
-        crowd = batch(W)
+        crowd = _grouped_env(names, W, seed, device, _backend)
         crowd.reset()
         best, rank, _ = crowd.tabu_blocks(rank, polish, int(tenure))
     mk = host(best).astype(np.int32)
-    by_group = np.where(mk >= 0, mk.astype(np.int64), np.iinfo(np.int64).max).reshape(G, W)
-    walker = by_group.argmin(axis=1).astype(np.int32)                # (the first of equal makespans)
-    winner = (np.arange(G) * W + walker).astype(np.int32)
+    walker, winner = _group_winners(mk, G, W)
     best_rank = host(rank)[winner].copy()
     again, start = env.evaluate_order(best_rank, np.arange(G, dtype=np.int32), start=True)
     assert np.array_equal(host(again), mk[winner])
@@ -1761,18 +1638,6 @@ def bottleneck_search(instances, walkers=64, reopt=1, spread=50, polish=0, tenur
 
 
 # ---- Carlier's one-machine search, shifting bottleneck constructions sequenced by it (include/jss_carlier.h) --------------------
-def carlier_library(backend):
-    """The library of ``backend`` that exports include/jss_carlier.h: ``backend.carlier_lib`` (HipBackend: libjss_carlier_hip.so,
-    loaded on first use; CpuBackend: the twin), else ``backend.lib`` itself when it carries the symbols."""
-    lib = getattr(backend, "carlier_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.CARLIER_SYMBOLS):
-            raise RuntimeError("solve_machines: the backend's library does not export include/jss_carlier.h")
-        _abi.bind_carlier(lib)
-    return lib
-
-
 def carlier_reference(r, p, q, nodes):
     """include/jss_carlier.h's one-machine search, written from the header: the operations by ascending flat index with heads
     ``r``, durations ``p`` and tails ``q``, a budget of ``nodes``.  Returns ``(opt, proved, low, nodes_used, starts)``."""
@@ -1954,18 +1819,6 @@ def bottleneck_exact_reference(env_const, ops, parents=None, bias=None, reopt=1,
 
 # ---- constraint propagation on operation windows, destructive lower bounds (include/jss_propagate.h) ---------------------------
 PROPAGATE_RULES = ("job", "fixed", "pairs", "overload", "after", "before")
-
-
-def propagate_library(backend):
-    """The library of ``backend`` that exports include/jss_propagate.h: ``backend.propagate_lib`` (HipBackend:
-    libjss_propagate_hip.so, CpuBackend: the twin), else ``backend.lib`` where it exports the call."""
-    lib = getattr(backend, "propagate_lib", None)
-    if lib is None:
-        lib = backend.lib
-        if not all(hasattr(lib, name) for name in _abi.PROPAGATE_SYMBOLS):
-            raise RuntimeError("propagate: the backend's library does not export include/jss_propagate.h")
-        _abi.bind_propagate(lib)
-    return lib
 
 
 def _task_intervals(est, lct, d, rules, slack):
@@ -2193,12 +2046,7 @@ def _pack_destructive(rows, one_machine, upper, env):
 
 
 def _destructive_args(what, instances, upper, rounds, span, passes):
-    if isinstance(instances, (PackedBatch, BatchedJssEnv)) or type(instances).__name__ in ("BucketedJssEnv", "JssVectorEnv", "JssEnv"):
-        raise NotImplementedError(f"{what} takes instances (a name, a path, an Instance, or a list of them): call propagate on a "
-                                  "BatchedJssEnv for anything else")
-    names = [instances] if isinstance(instances, (str, os.PathLike, Instance)) else list(instances)
-    if len(names) < 1:
-        raise ValueError(f"{what}: need at least one instance")
+    names, _ = _instance_groups(what, instances, "call propagate on a BatchedJssEnv for anything else")
     if int(rounds) < 0 or int(span) < 1 or not 1 <= int(passes) <= _abi.PROPAGATE_MAX_PASSES:
         raise ValueError(f"{what}: rounds >= 0, span >= 1, passes in [1, {_abi.PROPAGATE_MAX_PASSES}]")
     uppers = [None] * len(names) if upper is None else [int(x) for x in np.broadcast_to(np.asarray(upper, np.int64), (len(names),))]
@@ -2226,8 +2074,7 @@ def destructive_bound(instances, upper=None, shave=True, rounds=8, span=64, pass
     Returns a ``DestructiveResult``."""
     names, uppers = _destructive_args("destructive_bound", instances, upper, rounds, span, passes)
     G = len(names)
-    kw = dict(device=device) if _backend is None else dict(_backend=_backend)
-    env = BatchedJssEnv(names[0], batch=1, **kw) if G == 1 else BatchedJssEnv(names, batch=G, table_of_env=np.arange(G), order="interleaved", **kw)
+    env = _grouped_env(names, 1, 0, device, _backend)
     be = env.backend
     env.reset()
     host = lambda x: np.asarray(be.numpy(x))   # noqa: E731
@@ -2251,8 +2098,7 @@ def destructive_reference(instances, upper=None, shave=True, rounds=8, span=64, 
     from .env import CpuBackend
     names, uppers = _destructive_args("destructive_reference", instances, upper, rounds, span, passes)
     G = len(names)
-    kw = dict(_backend=CpuBackend(threads=1))
-    env = BatchedJssEnv(names[0], batch=1, **kw) if G == 1 else BatchedJssEnv(names, batch=G, table_of_env=np.arange(G), order="interleaved", **kw)
+    env = _grouped_env(names, 1, 0, None, CpuBackend(threads=1))
     env.reset()
     const = np.asarray(env.backend.numpy(env.env_const)).reshape(-1, _abi.NC)
     ops = np.asarray(env.packed.ops).reshape(-1, env.jmax, env.mmax)

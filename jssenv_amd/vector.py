@@ -21,8 +21,10 @@ from typing import Optional
 
 from .env import BatchedJssEnv
 from .facade import gymnasium_base
+from .search_calls import refuses_search_calls
 
 
+@refuses_search_calls
 class JssVectorEnv(gymnasium_base("VectorEnv")):
     """(a ``gymnasium.vector.VectorEnv`` when gymnasium is importable; its attributes are set here directly, the base
     class's constructor -- whose signature differs between gymnasium 0.29 and 1.x -- is not called)"""
@@ -99,54 +101,6 @@ class JssVectorEnv(gymnasium_base("VectorEnv")):
     @property
     def makespan(self):
         return self._out(self.env.makespan)
-
-    def evaluate_order(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not evaluate machine orders: call evaluate_order on a BatchedJssEnv "
-                                  "(search.improve takes one, or a list of instances)")
-
-    def tabu(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu on a BatchedJssEnv "
-                                  "(search.tabu_search takes a list of instances)")
-
-    def tabu_blocks(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not run tabu search: call tabu_blocks on a BatchedJssEnv "
-                                  "(search.tabu_search takes a list of instances)")
-
-    def relink(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not relink machine orders: call relink on a BatchedJssEnv "
-                                  "(search.relink_search takes a list of instances)")
-
-    def order_distance(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not relink machine orders: call order_distance on a BatchedJssEnv "
-                                  "(search.relink_search takes a list of instances)")
-
-    def decode_keys(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not decode key tables: call decode_keys on a BatchedJssEnv "
-                                  "(search.brkga_search takes a list of instances)")
-
-    def evolve_keys(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not evolve key tables: call evolve_keys on a BatchedJssEnv "
-                                  "(search.brkga_search takes a list of instances)")
-
-    def relax_machines(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not relax partial selections: call relax_machines on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def bottleneck(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def solve_machines(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not solve one-machine problems: call solve_machines on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def bottleneck_exact(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not build machine orders: call bottleneck_exact on a BatchedJssEnv "
-                                  "(search.bottleneck_search takes a list of instances)")
-
-    def propagate(self, *args, **kwargs):
-        raise NotImplementedError("JssVectorEnv does not propagate operation windows: call propagate on a BatchedJssEnv "
-                                  "(search.destructive_bound takes a list of instances)")
 
     def close(self, **kwargs):
         self.env.synchronize()
